@@ -6,9 +6,10 @@ search (levels 0..5: level-0 bitmap build, per-level neighbour compaction, CI sw
 the block's correlation matrix, which is already resident in HBM when the timed region starts.  Workload = the
 north_star headline: 10,000 SNPs x 20 traits, N = 16,384 individuals, alpha = 1e-4, max level 5; the matrix is
 produced from synthetic packed .bed genotypes by this repo's own correlation build (Kendall-npn SNP x SNP, Pearson
-SNP x trait / trait x trait), exactly what `cusk` feeds its sweep.  The same run checks the engine's adjacency and
-separating sets against the CPU oracle on the full block (`parity`), times the CPU baselines, and adds a bounded
-whole-chromosome pass through the multi-GPU block driver on this one GPU (`chromosome`).
+SNP x trait / trait x trait), exactly what `cusk` feeds its sweep.  With --full the same run also checks the engine's
+adjacency and separating sets against the CPU oracle on the full block (`parity`), times the CPU baselines, adds the
+per-level table and rooflines, the end-to-end block and a bounded whole-chromosome pass through the multi-GPU block
+driver on this one GPU (`scale`).
 
 N > 1 (torchrun, one rank per GPU): BASELINE.json config 4, the whole-chromosome run -- 25 unequal LD blocks per GPU
 (200 blocks x ~500 SNPs x 20 traits on 8 GPUs; weak scaling), written as a PLINK file set, every block through the
@@ -19,12 +20,14 @@ blocks of a batch in one set of device runs; .bed staged in HBM once per GPU), n
 which writes every file; the gather and rank 0's writing are timed separately.  --writer merge: every rank writes the
 files of its own blocks and the merged skeleton -- what `merge-block-outputs` reads of every block -- is gathered to rank
 0, which writes merged_blocks* from memory (the library's merge); --writer local has no exchange (what the reference's
-one-process-per-block runs do).  Every line reports all three.  One step = one pass of the job over the whole chromosome.
+one-process-per-block runs do).  A --full line reports all three.  One step = one pass of the job over the whole chromosome.
 
-EVERY line (N = 1 included) carries the same `scale` object -- the whole-chromosome job on this many GPUs, 25 blocks per
-GPU -- and `scale.blocks_per_sec` is the key a scaling curve is to be built from (at N = 1 `value` is the headline block,
-at N > 1 the chromosome job: not comparable with each other).
+EVERY --full line (N = 1 included) and every N > 1 line carries the same `scale` object -- the whole-chromosome job on this
+many GPUs, 25 blocks per GPU -- and `scale.blocks_per_sec` is the key a scaling curve is to be built from (at N = 1 `value`
+is the headline block, at N > 1 the chromosome job: not comparable with each other).
 
+A plain run (no --full) does only what the headline figure needs: set-up, --warmup steps, the --steps timed steps, the
+outputs of the last step when --dump-outputs DIR is given, and the line (metric, value, unit, ms_per_step, ...).
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -270,10 +273,11 @@ def chromosome_run(args, rank, world, device, cdev, dist, steps, warmup):
         return dt, ex, ca, {k_: v_ / K for k_, v_ in ph.items()}, {k_: v_ / K * 1e3 for k_, v_ in tms.items()}, nwritten
 
     one_pass(args.writer)  # first pass of the process: allocations, staging of the .bed
-    _, detail_stats, _ = one_pass("local", timing=1)
+    # --full: the untimed detail pass (per-level kernel times of the roofline) and the other writers' timed passes
+    detail_stats = one_pass("local", timing=1)[1] if args.full else []
     dt, ex, ca, ph, tms, nwritten = timed(args.writer, steps, warmup)
     others = {}
-    for other in ("merge", "rank0", "local"):
+    for other in ("merge", "rank0", "local") if args.full else ():
         if other == args.writer or (other == "merge" and bv <= 0):
             continue
         dt2, _ex2, _ca2, _ph2, tms2, _nw2 = timed(other, steps, 1)
@@ -281,7 +285,7 @@ def chromosome_run(args, rank, world, device, cdev, dist, steps, warmup):
                          "gather_ms": tms2.get("gather_s", 0.0) if other != "local" else 0.0, "write_ms": tms2.get("write_s")}
     # per-level totals over this rank's blocks (detail pass): which kernel dominates the device time
     lv_ms, lv_tests, lv_sub, nvar = np.zeros(15), np.zeros(15), np.zeros(15), 0
-    for s_ in (detail_stats if bv > 0 else detail_stats.values()):
+    for s_ in (detail_stats if bv > 0 or not detail_stats else detail_stats.values()):
         for st in (s_.stage[0], s_.stage[1]):
             for l in range(st.levels_run):
                 lv_ms[l] += st.main_kernel_ms[l]
@@ -389,6 +393,116 @@ def e2e_block(args, bed, phen, means, stds, device):
         shutil.rmtree(dout, ignore_errors=True)
 
 
+DUMP_MAX_ROWS = {"edges": 1 << 20, "sepsets": 1 << 18}  # 16 MB + 37.7 MB of float64, + pMax and counters: < 64 MB in all
+
+
+def _seeded_rows(count, cap, seed):
+    """all row indices when count <= cap, else a fixed seeded sample of cap of them (ascending)"""
+    if count <= cap:
+        return np.arange(count)
+    return np.sort(np.random.default_rng(seed).choice(count, cap, replace=False))
+
+
+def dump_outputs(d, eng, Cd, st, engine):
+    """--dump-outputs DIR: what the last timed step returned to its caller, as DIR/<name>.npy (float64 / float32).
+    edges [E, 2] = (i, j), i < j, of the skeleton (the whole adjacency); canonical_tests = the device counter per level
+    and, last, the level reached; cusk only: sepsets [R, 18] = (x, y, level, z, S[14], -1 padded) records sorted by
+    (x, y), pmax_edges / pmax_sepsets = pMax at those pairs.  Above DUMP_MAX_ROWS rows a fixed seeded sample is written."""
+    os.makedirs(d, exist_ok=True)
+    G = eng.adjacency()
+    ei, ej = np.nonzero(G)
+    del G
+    up = ei < ej
+    ei, ej = ei[up], ej[up]
+    r = _seeded_rows(len(ei), DUMP_MAX_ROWS["edges"], 1)
+    ei, ej = ei[r], ej[r]
+    np.save(os.path.join(d, "edges.npy"), np.stack([ei, ej], axis=1).astype(np.float64))
+    np.save(os.path.join(d, "canonical_tests.npy"), np.array(list(st.canonical_tests) + [st.level], np.float64))
+    if engine != "cusk":
+        return
+    x, y, lv, z, S = eng.sepsets()
+    r = _seeded_rows(len(x), DUMP_MAX_ROWS["sepsets"], 2)
+    x, y, lv, z, S = x[r], y[r], lv[r], z[r], S[r]
+    rec = np.concatenate([np.stack([x, y, lv], axis=1).astype(np.float64), z.astype(np.float64)[:, None], S.astype(np.float64)], axis=1)
+    np.save(os.path.join(d, "sepsets.npy"), rec)
+    P = eng.pmax(Cd.ptr)
+    np.save(os.path.join(d, "pmax_edges.npy"), P[ei, ej].astype(np.float32))
+    np.save(os.path.join(d, "pmax_sepsets.npy"), P[x, y].astype(np.float32))
+
+
+def full_block_detail(out, args, st, n, m, N, lv, main_ms, main_detail, kernel_ms, level_ms, D, corr_ms):
+    """--full, block workload: the rooflines of the dominant kernel and of every level, the per-level table of the detail
+    pass and the correlation build's timing, added to the line `out`"""
+    # levels other than the dominant one: their kernel durations come from the detail pass
+    for l in range(15):
+        if l != lv:
+            main_ms[l] = main_detail[l]
+    # dominant kernel = the level whose sweep kernel takes the most device time; its duration comes from HIP
+    # events the engine records on its own stream around that kernel alone (cusk_stats.main_kernel_ms)
+    # HBM-side bytes per launch from the committed PMC passes (profiles/pmc_traffic.json: the headline block's cusk
+    # engine; FETCH_SIZE corrected as the guide prescribes for gfx950, x 2 -- the run's own calibration beside it)
+    traffic, traffic_detail = None, None
+    tf = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    if os.path.exists(tf) and args.engine == "cusk":
+        try:
+            tj = json.load(open(tf))
+            traffic = tj.get(f"level{lv}")
+            traffic_detail = {k: v for k, v in tj.items() if k != "note" and (k.startswith(f"level{lv}") or k in ("fetch_calibration", "kernel"))}
+        except Exception:  # noqa: BLE001
+            traffic = None
+    out["roofline"] = roofline_of(lv, st.tests[lv], st.subsets[lv], n, main_ms[lv], args.engine, traffic)
+    out["roofline_counts"] = "tests and conditioning sets the dominant kernel EXECUTED in one launch (device counters)"
+    out["level_rooflines"] = {str(l): {k: v for k, v in roofline_of(l, st.tests[l], st.subsets[l], n, main_ms[l], args.engine).items()
+                                       if k in ("bound", "achieved", "peak", "unit", "frac", "kernel_ms_per_step", "lds")}
+                              for l in range(st.levels_run) if main_ms[l] > 0}
+    out["corr_roofline"] = {
+        "kernel": "mxm_fp4_kernel<true> (v_mfma_scale_f32_32x32x64_f8f6f4 on e2m1 indicators, nine contingency GEMMs, "
+                  "upper-triangle tiles, .bed decoded in-kernel)",
+        "bound": "mfma",
+        "achieved": (2.0 * 9.0 * N * m * (m - 1) / 2.0) / (corr_ms[1] * 1e-3) / 1e12 if corr_ms[1] > 0 else 0.0,
+        "peak": 10000.0,
+        "unit": "TOP/s",
+        "frac": ((2.0 * 9.0 * N * m * (m - 1) / 2.0) / (corr_ms[1] * 1e-3) / 1e12) / 10000.0 if corr_ms[1] > 0 else 0.0,
+        "dtype": "fp4 (e2m1) operands, f32 accumulation, exact for 0/1 indicators",
+        "frac_of_int8_peak": ((2.0 * 9.0 * N * m * (m - 1) / 2.0) / (corr_ms[1] * 1e-3) / 1e12) / 5000.0 if corr_ms[1] > 0 else 0.0,
+        "note": "ops = 2*9*N*m(m-1)/2 (SURVEY 8d); peak = dense FP4 MFMA (~10 PF, MI355X_MICROARCH.md), the pipe the kernel "
+                "runs on; frac_of_int8_peak = the same rate against SURVEY 8d's 5 POPS int8 figure",
+    }
+    out["levels"] = {
+        str(l): {"tests": int(st.tests[l]), "subsets": int(st.subsets[l]), "removed": int(st.removed[l]), "rechecks": int(st.rechecks[l]),
+                 "max_degree": int(st.max_degree[l]), "sweep_ms": float(kernel_ms[l]), "level_ms": float(level_ms[l])}
+        for l in range(st.levels_run)
+    }
+    out["levels_note"] = (f"sweep_ms / level_ms and the durations of level_rooflines other than level {lv}: detail pass of {D} untimed steps "
+                          "with per-level HIP events (timing = 1); the timed steps record only the pair around the dominant kernel")
+    out["corr_build_ms"] = {"decode": corr_ms[0], "snp_x_snp": corr_ms[1], "snp_trait_and_trait_trait": corr_ms[2],
+                            "total_incl_h2d": corr_ms[3]}
+    if traffic_detail:
+        out["roofline"]["traffic_detail"] = traffic_detail
+    if args.engine == "cusk" and sum(st.canonical_tests) > 0:
+        # the dominant kernel's roofline on the CANONICAL tests of its level: the engine executes more tests than that
+        # (lanes cannot see each other's fresh verdicts; level 1 evaluates every pair), so this is the figure that cannot be
+        # inflated by doing needless work; roofline_executed = the same with the launch's own test counter
+        ex_r = out["roofline"]
+        out["roofline"] = roofline_of(lv, int(st.canonical_tests[lv]), int(st.subsets[lv]), n, main_ms[lv], args.engine, traffic)
+        if traffic_detail:
+            out["roofline"]["traffic_detail"] = traffic_detail
+        out["roofline_counts"] = ("tests of the dominant kernel's level in the CANONICAL (sequential) schedule (device counter, equal to "
+                                  "the oracle's count: parity.canonical_count_equal)")
+        # NOT a roofline (the operands of the extra tests come from LDS, not HBM): how many tests the launch executed per second
+        out["dominant_kernel_executed_tests"] = {"tests_per_launch": int(st.tests[lv]), "tests_per_sec": float(st.tests[lv]) / (main_ms[lv] * 1e-3) if main_ms[lv] > 0 else 0.0,
+                                                 "bytes_equivalent_per_sec": ex_r["achieved"] * 1e9,
+                                                 "note": "the launch evaluates every pair of a row (lanes cannot see each other's fresh verdicts); the byte figure prices those tests "
+                                                         "with SURVEY 8(d)'s 12 B as if their operands came from HBM -- they come from LDS, so this is a rate, not a roofline fraction"}
+    elif args.engine == "cuskss" and st.canonical_tests[lv] > 0:
+        # hetcor engine: the finaliser of level 1 counts the canonical tests on the device (cusk_stats.canonical_tests[1]; the
+        # deeper levels are not counted there): the dominant kernel's roofline is on canonical tests, as the cusk line's
+        ex_r = out["roofline"]
+        out["roofline"] = roofline_of(lv, int(st.canonical_tests[lv]), int(st.subsets[lv]), n, main_ms[lv], args.engine, traffic)
+        out["roofline_counts"] = "tests of the dominant kernel's level in the CANONICAL (sequential) schedule (device counter of level1_apply_kernel)"
+        out["dominant_kernel_executed_tests"] = {"tests_per_launch": int(st.tests[lv]), "tests_per_sec": float(st.tests[lv]) / (main_ms[lv] * 1e-3) if main_ms[lv] > 0 else 0.0,
+                                                 "bytes_equivalent_per_sec": ex_r["achieved"] * 1e9, "note": "a rate, not a roofline fraction (see the cusk line)"}
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -423,6 +537,14 @@ def main():
                     help="engine option for kernel experiments (cusk_set_option); the default run sets none")
     ap.add_argument("--cpu-sample-markers", type=int, default=10000)
     ap.add_argument("--cpu-threads", type=int, default=0, help="OpenMP threads of the CPU baseline (0 = min(16, affinity))")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-level detail pass and rooflines, correlation-build timing, "
+                         "full-size parity against the CPU oracle and the CPU baselines, the end-to-end block, the whole-chromosome "
+                         "pass (N = 1) and the other writers (chromosome workload).  A plain run sets up, warms up, times --steps "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="block workload: after the timed steps, write what the last step returned to its caller as DIR/<name>.npy "
+                         "(float32 / float64, <= 64 MB in all; see dump_outputs)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -431,6 +553,10 @@ def main():
     if world != args.gpus and world == 1 and args.gpus > 1:
         print(f"bench.py: --gpus {args.gpus} needs torchrun (WORLD_SIZE={world})", file=sys.stderr)
         sys.exit(2)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.workload == "chromosome" or (args.workload == "auto" and world > 1)):
+        ap.error("--dump-outputs: the block workload only (the chromosome job's results are its files)")
     import torch
     import torch.distributed as dist
 
@@ -465,11 +591,12 @@ def main():
                                 "scale.executed_ci_tests_per_sec = what the parallel sweeps executed",
                 "blocks_per_sec": scale["blocks_per_sec"],
                 "scaling_curve_key": scale["curve_key"],
-                "roofline": roofline_of(lv, lv_tests[lv], lv_sub[lv], nvar, lv_ms[lv], "cusk"),
                 "scale": scale,
             }
-            out["roofline"]["note"] = ("rank 0's batches of an untimed detail pass (per-level HIP events on), summed over batches and both stages: the level whose dominant kernel "
-                                       "takes the most device time; " + out["roofline"]["note"])
+            if args.full:
+                out["roofline"] = roofline_of(lv, lv_tests[lv], lv_sub[lv], nvar, lv_ms[lv], "cusk")
+                out["roofline"]["note"] = ("rank 0's batches of an untimed detail pass (per-level HIP events on), summed over batches and both stages: the level whose "
+                                           "dominant kernel takes the most device time; " + out["roofline"]["note"])
             print(json.dumps(out))
         if world > 1:
             dist.barrier()
@@ -499,9 +626,10 @@ def main():
         k, v = kv.split("=")
         eng.set_option(k, int(v))
     Cd = cg.DeviceArray(nbytes=4 * n * n)
-    eng.corr_build(bed, phen, m, N, p, means, stds, Cd.ptr)  # warm
     eng.corr_build(bed, phen, m, N, p, means, stds, Cd.ptr)
-    corr_ms = [float(x) for x in eng.corr_timing()]
+    if args.full:  # a second, warm build for corr_build_ms / corr_roofline
+        eng.corr_build(bed, phen, m, N, p, means, stds, Cd.ptr)
+        corr_ms = [float(x) for x in eng.corr_timing()]
 
     Th = cg.threshold_array(N, args.alpha)
     th_het = cg.hetcor_threshold(args.alpha)
@@ -511,28 +639,31 @@ def main():
             return eng.run_skeleton(Cd.ptr, n, Th, args.max_level)
         return eng.run_hetcor(Cd.ptr, n, th_het, args.max_level, ess_uniform=float(N))
 
+    if not args.full and not any(kv.split("=")[0] == "timing" for kv in args.option):
+        eng.set_option("timing", 0)  # a plain run records no per-level HIP events: nothing reads them
     for _ in range(args.warmup):
         st = step()
-    # Detail pass (untimed): per-level events (option timing = 1: a pair around every level's sweep) for the `levels` table
-    # and the per-level rooflines.  Every HIP event costs a few microseconds of device time (a dozen per step: ~50 us of
-    # a 1.3 ms step), so the timed steps below record only the pair around the dominant kernel (timing = 3) -- the
-    # roofline's duration is still measured live, inside the timed region, on the engine's own stream.
-    D = 5
-    kernel_ms = np.zeros(15)
-    level_ms = np.zeros(15)
-    main_detail = np.zeros(15)
-    eng.set_option("timing", 1)
-    for _ in range(D):
-        st = step()
-        kernel_ms += np.array(st.kernel_ms)
-        level_ms += np.array(st.level_ms)
-        main_detail += np.array(st.main_kernel_ms)
-    kernel_ms /= D
-    level_ms /= D
-    main_detail /= D
-    lv = int(np.argmax(main_detail[1:]) + 1) if st.levels_run > 1 else 0
-    eng.set_option("timing", 3 if lv == 1 else 1)
-    st = step()
+    if args.full:
+        # Detail pass (untimed): per-level events (option timing = 1: a pair around every level's sweep) for the `levels`
+        # table and the per-level rooflines.  Every HIP event costs a few microseconds of device time (a dozen per step:
+        # ~50 us of a 1.3 ms step), so the timed steps below record only the pair around the dominant kernel (timing = 3)
+        # -- the roofline's duration is still measured live, inside the timed region, on the engine's own stream.
+        D = 5
+        kernel_ms = np.zeros(15)
+        level_ms = np.zeros(15)
+        main_detail = np.zeros(15)
+        eng.set_option("timing", 1)
+        for _ in range(D):
+            st = step()
+            kernel_ms += np.array(st.kernel_ms)
+            level_ms += np.array(st.level_ms)
+            main_detail += np.array(st.main_kernel_ms)
+        kernel_ms /= D
+        level_ms /= D
+        main_detail /= D
+        lv = int(np.argmax(main_detail[1:]) + 1) if st.levels_run > 1 else 0
+        eng.set_option("timing", 3 if lv == 1 else 1)
+    st = step()  # untimed: the first step after the last change of options (and the only one before the clock with --warmup 0)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     tests_total = 0
@@ -543,26 +674,11 @@ def main():
         main_ms += np.array(st.main_kernel_ms)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, Cd, st, args.engine)
 
     K = args.steps
     main_ms /= K
-    # levels other than the dominant one: their kernel durations come from the detail pass
-    for l in range(15):
-        if l != lv:
-            main_ms[l] = main_detail[l]
-    # dominant kernel = the level whose sweep kernel takes the most device time; its duration comes from HIP
-    # events the engine records on its own stream around that kernel alone (cusk_stats.main_kernel_ms)
-    # HBM-side bytes per launch from the committed PMC passes (profiles/pmc_traffic.json: the headline block's cusk
-    # engine; FETCH_SIZE corrected as the guide prescribes for gfx950, x 2 -- the run's own calibration beside it)
-    traffic, traffic_detail = None, None
-    tf = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(tf) and args.engine == "cusk":
-        try:
-            tj = json.load(open(tf))
-            traffic = tj.get(f"level{lv}")
-            traffic_detail = {k: v for k, v in tj.items() if k != "note" and (k.startswith(f"level{lv}") or k in ("fetch_calibration", "kernel"))}
-        except Exception:  # noqa: BLE001
-            traffic = None
     headline = (m == 10000 and p == 20 and N == 16384 and args.max_level == 5 and args.engine == "cusk")
     out = {
         "metric": "ci_tests_per_sec",
@@ -589,69 +705,21 @@ def main():
         "executed_tests_per_step": tests_total / K,
         "canonical_tests_per_step_device": int(sum(st.canonical_tests)) if args.engine == "cusk" else None,
         "canonical_tests_by_level_device": [int(v) for v in st.canonical_tests[: st.levels_run]],
-        "roofline": roofline_of(lv, st.tests[lv], st.subsets[lv], n, main_ms[lv], args.engine, traffic),
-        "roofline_counts": "tests and conditioning sets the dominant kernel EXECUTED in one launch (device counters)",
-        "level_rooflines": {str(l): {k: v for k, v in roofline_of(l, st.tests[l], st.subsets[l], n, main_ms[l], args.engine).items()
-                                     if k in ("bound", "achieved", "peak", "unit", "frac", "kernel_ms_per_step", "lds")}
-                            for l in range(st.levels_run) if main_ms[l] > 0},
-        "corr_roofline": {
-            "kernel": "mxm_fp4_kernel<true> (v_mfma_scale_f32_32x32x64_f8f6f4 on e2m1 indicators, nine contingency GEMMs, "
-                      "upper-triangle tiles, .bed decoded in-kernel)",
-            "bound": "mfma",
-            "achieved": (2.0 * 9.0 * N * m * (m - 1) / 2.0) / (corr_ms[1] * 1e-3) / 1e12 if corr_ms[1] > 0 else 0.0,
-            "peak": 10000.0,
-            "unit": "TOP/s",
-            "frac": ((2.0 * 9.0 * N * m * (m - 1) / 2.0) / (corr_ms[1] * 1e-3) / 1e12) / 10000.0 if corr_ms[1] > 0 else 0.0,
-            "dtype": "fp4 (e2m1) operands, f32 accumulation, exact for 0/1 indicators",
-            "frac_of_int8_peak": ((2.0 * 9.0 * N * m * (m - 1) / 2.0) / (corr_ms[1] * 1e-3) / 1e12) / 5000.0 if corr_ms[1] > 0 else 0.0,
-            "note": "ops = 2*9*N*m(m-1)/2 (SURVEY 8d); peak = dense FP4 MFMA (~10 PF, MI355X_MICROARCH.md), the pipe the kernel "
-                    "runs on; frac_of_int8_peak = the same rate against SURVEY 8d's 5 POPS int8 figure",
-        },
-        "levels": {
-            str(l): {"tests": int(st.tests[l]), "subsets": int(st.subsets[l]), "removed": int(st.removed[l]), "rechecks": int(st.rechecks[l]),
-                     "max_degree": int(st.max_degree[l]), "sweep_ms": float(kernel_ms[l]), "level_ms": float(level_ms[l])}
-            for l in range(st.levels_run)
-        },
-        "levels_note": f"sweep_ms / level_ms and the durations of level_rooflines other than level {lv}: detail pass of {D} untimed steps "
-                       "with per-level HIP events (timing = 1); the timed steps record only the pair around the dominant kernel",
         "headline_block_sweeps_per_sec": K / dt,
         "filter_violations": int(st.violations), "exact_fallbacks": int(st.exact_fallbacks),
-        "corr_build_ms": {"decode": corr_ms[0], "snp_x_snp": corr_ms[1], "snp_trait_and_trait_trait": corr_ms[2],
-                          "total_incl_h2d": corr_ms[3]},
         "synth_gen_s": t_gen,
+        "full": bool(args.full),
     }
-    if traffic_detail:
-        out["roofline"]["traffic_detail"] = traffic_detail
     if args.engine == "cusk" and sum(st.canonical_tests) > 0:
         # `value` = canonical CI tests (the sequential schedule of the reference algorithm, computed on the device from
-        # the selected ranks and checked against the oracle's own count below) over the measured time
+        # the selected ranks and checked against the oracle's own count in --full runs) over the measured time
         out["value_executed"] = out["value"]
         out["value"] = float(sum(st.canonical_tests)) / (dt / K)
         out["value_counts"] = ("canonical CI tests (sequential schedule; cusk_stats.canonical_tests, device counter) / measured time; "
                                "value_executed = executed tests (device counters) / the same time")
-        # the dominant kernel's roofline on the CANONICAL tests of its level: the engine executes more tests than that
-        # (lanes cannot see each other's fresh verdicts; level 1 evaluates every pair), so this is the figure that cannot be
-        # inflated by doing needless work; roofline_executed = the same with the launch's own test counter
-        ex_r = out["roofline"]
-        out["roofline"] = roofline_of(lv, int(st.canonical_tests[lv]), int(st.subsets[lv]), n, main_ms[lv], args.engine, traffic)
-        if traffic_detail:
-            out["roofline"]["traffic_detail"] = traffic_detail
-        out["roofline_counts"] = ("tests of the dominant kernel's level in the CANONICAL (sequential) schedule (device counter, equal to "
-                                  "the oracle's count: parity.canonical_count_equal)")
-        # NOT a roofline (the operands of the extra tests come from LDS, not HBM): how many tests the launch executed per second
-        out["dominant_kernel_executed_tests"] = {"tests_per_launch": int(st.tests[lv]), "tests_per_sec": float(st.tests[lv]) / (main_ms[lv] * 1e-3) if main_ms[lv] > 0 else 0.0,
-                                                 "bytes_equivalent_per_sec": ex_r["achieved"] * 1e9,
-                                                 "note": "the launch evaluates every pair of a row (lanes cannot see each other's fresh verdicts); the byte figure prices those tests "
-                                                         "with SURVEY 8(d)'s 12 B as if their operands came from HBM -- they come from LDS, so this is a rate, not a roofline fraction"}
-    elif args.engine == "cuskss" and st.canonical_tests[lv] > 0:
-        # hetcor engine: the finaliser of level 1 counts the canonical tests on the device (cusk_stats.canonical_tests[1]; the
-        # deeper levels are not counted there): the dominant kernel's roofline is on canonical tests, as the cusk line's
-        ex_r = out["roofline"]
-        out["roofline"] = roofline_of(lv, int(st.canonical_tests[lv]), int(st.subsets[lv]), n, main_ms[lv], args.engine, traffic)
-        out["roofline_counts"] = "tests of the dominant kernel's level in the CANONICAL (sequential) schedule (device counter of level1_apply_kernel)"
-        out["dominant_kernel_executed_tests"] = {"tests_per_launch": int(st.tests[lv]), "tests_per_sec": float(st.tests[lv]) / (main_ms[lv] * 1e-3) if main_ms[lv] > 0 else 0.0,
-                                                 "bytes_equivalent_per_sec": ex_r["achieved"] * 1e9, "note": "a rate, not a roofline fraction (see the cusk line)"}
-    if not args.no_cpu_baseline:
+    if args.full:
+        full_block_detail(out, args, st, n, m, N, lv, main_ms, main_detail, kernel_ms, level_ms, D, corr_ms)
+    if args.full and not args.no_cpu_baseline:
         nall = args.cpu_threads or min(16, len(os.sched_getaffinity(0)))
         from oracle import oracle as O
 
@@ -745,10 +813,10 @@ def main():
         del Ch, sub, sub1, ref, r64
     Cd.free()
     eng.close()
-    if headline or args.e2e:
+    if (args.full and headline) or args.e2e:
         out["e2e_block"] = e2e_block(args, bed, phen, means, stds, local_rank)
         out["e2e_block_ms"] = out["e2e_block"]["e2e_block_ms"]
-    if not args.no_chromosome:
+    if args.full and not args.no_chromosome:
         a2 = argparse.Namespace(**vars(args))
         scale, _lvs, _dt, _tests = chromosome_run(a2, 0, 1, local_rank, None, None, args.scale_steps, 1)
         out["scale"] = scale

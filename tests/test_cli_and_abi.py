@@ -123,17 +123,41 @@ def test_prep_bed_subcommand():
     assert a.bfiles == "data/chr" and a.func is cli.prep_bed
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/cusk/include/mps"), reason="needs the reference's headers (build container only)")
+LIB_DIR = os.path.join(ROOT, "ci-gwas_amd", "csrc")
+
+
+def _nm(*args):
+    import subprocess
+
+    r = subprocess.run(["nm", *args], capture_output=True, text=True, check=True)
+    return {ln.split()[-1] for ln in r.stdout.splitlines() if ln.strip()}
+
+
+def undefined_symbols(obj):
+    return _nm("-u", obj)
+
+
+def library_symbols():
+    return _nm("-D", "--defined-only", os.path.join(LIB_DIR, "libcusk_hip.so"))
+
+
 def test_reference_headers_link_against_the_library_unchanged(tmp_path):
     """A TU that includes the reference's <mps/corr_host.h> and <mps/cuPC_call_prep.h> links against libcusk_hip.so:
     the C++-linkage names cu_corr_pearson_npn, cu_marker_phen_corr_pearson, threshold_array, hetcor_threshold,
-    std_normal_qnorm resolve with the reference's signatures, Skeleton / hetcor_skeleton with C linkage."""
+    std_normal_qnorm resolve with the reference's signatures, Skeleton / hetcor_skeleton with C linkage.  The library
+    symbols such a TU refers to are stored (tests/golden/ref_link_symbols.json, from link_ref_headers.cpp built on the
+    reference's headers); link_ref_decls.cpp makes the same calls and must refer to exactly those, link and run."""
+    import json
     import subprocess
 
-    lib_dir = os.path.join(ROOT, "ci-gwas_amd", "csrc")
-    exe = str(tmp_path / "link_ref")
-    r = subprocess.run(["g++", "-std=c++20", "-I/root/reference/cusk/include", os.path.join(ROOT, "tests", "link_ref", "link_ref_headers.cpp"),
-                        "-L" + lib_dir, "-lcusk_hip", "-Wl,-rpath," + lib_dir, "-o", exe], capture_output=True, text=True)
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_link_symbols.json")))["symbols"]
+    obj, exe = str(tmp_path / "link_ref.o"), str(tmp_path / "link_ref")
+    r = subprocess.run(["g++", "-std=c++20", "-c", os.path.join(ROOT, "tests", "link_ref", "link_ref_decls.cpp"), "-o", obj],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert sorted(undefined_symbols(obj) & library_symbols()) == want
+    assert set(want) <= library_symbols()
+    r = subprocess.run(["g++", obj, "-L" + LIB_DIR, "-lcusk_hip", "-Wl,-rpath," + LIB_DIR, "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0, out.stderr

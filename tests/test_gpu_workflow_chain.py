@@ -5,14 +5,15 @@
              -> merge-block-outputs -> cuskss-merged -> sepselect / orient-v-structs
 
 Every artefact is compared with the oracle pipeline fed the PREVIOUS artefact of the product (so a deviation cannot
-hide behind an earlier one): `.dim/.means/.stds` against the reference's own prep.cpp compiled in place (oracle/_ref,
-when present), the `.blocks` file against the oracle's blocking, per-block result files against the oracle's
-correlation build + two-stage skeleton on the packed genotypes, the merged files against oracle/merge_oracle.py (pinned
+hide behind an earlier one): `.dim/.means/.stds` against the files the reference's own prep.cpp wrote for the same
+PLINK set (tests/golden/ref_host_kat.npz), the `.blocks` file against the oracle's blocking, per-block result files
+against the oracle's correlation build + two-stage skeleton on the packed genotypes, the merged files against oracle/merge_oracle.py (pinned
 by files the reference wrote), `cuskss_merged.*` against the oracle's hetcor pipeline on the summary files, the
 sepselect outputs against oracle/sepselect_oracle.py (pinned by files the reference wrote).
 """
-import ctypes as C
+import hashlib
 import os
+import pathlib
 import shutil
 import socket
 import subprocess
@@ -23,7 +24,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SO = os.path.join(ROOT, "oracle", "_ref", "libref_host.so")
+REF_KAT = os.path.join(ROOT, "tests", "golden", "ref_host_kat.npz")
 M1, M2, N, P = 1300, 700, 1500, 6
 ALPHA, L1, L2, DEPTH = 1e-4, 3, 14, 1
 MAX_BLOCK, WIDTH = 400, 200
@@ -41,11 +42,10 @@ def _same(a, b):
     assert open(a, "rb").read() == open(b, "rb").read(), (a, b)
 
 
-@pytest.fixture(scope="module")
-def chain(tmp_path_factory, synth):
+def write_chain_inputs(d, synth):
     """PLINK file set of two chromosomes (no .dim/.means/.stds yet: `prep-bed` writes them) and a .phen whose traits
-    depend on 8 markers each plus a trait DAG"""
-    d = tmp_path_factory.mktemp("chain")
+    depend on 8 markers each plus a trait DAG, in directory d"""
+    d = pathlib.Path(d)
     m = M1 + M2
     rng = synth.rng_for(4242)
     G = synth.make_genotypes(m, N, rng, miss=0.002)
@@ -72,6 +72,18 @@ def chain(tmp_path_factory, synth):
     return dict(dir=d, stem=stem, phen=str(d / "y.phen"), bed=bed, chr_ids=chr_ids, m=m)
 
 
+def plink_sha256(stem):
+    h = hashlib.sha256()
+    for sfx in (".bed", ".bim", ".fam"):
+        h.update(open(stem + sfx, "rb").read())
+    return h.hexdigest()
+
+
+@pytest.fixture(scope="module")
+def chain(tmp_path_factory, synth):
+    return write_chain_inputs(tmp_path_factory.mktemp("chain"), synth)
+
+
 @pytest.mark.timeout(1500)
 def test_workflow_chain(chain, oracle, tmp_path):
     from cigwas_amd import cli
@@ -83,15 +95,11 @@ def test_workflow_chain(chain, oracle, tmp_path):
     # ---- 1. prep-bed (ci-gwas.py:386-387 -> `mps prep`) ----------------------------------------------------------------
     cli.main(["prep-bed", stem])
     assert open(stem + ".dim").read().split() == [str(N), str(m)]
-    if os.path.exists(REF_SO):
-        theirs = stem + "_ref"
-        for sfx in (".bed", ".bim", ".fam"):
-            os.link(stem + sfx, theirs + sfx)
-        L = C.CDLL(REF_SO)
-        L.ref_prep.restype = None
-        L.ref_prep(theirs.encode())
+    # the files the reference's prep.cpp wrote for this very PLINK set (tests/golden/make_ref_host_golden.py)
+    with np.load(REF_KAT) as z:
+        assert z["chain_prep/input_sha256"].tobytes().decode() == plink_sha256(stem), "chain inputs differ from the golden's"
         for sfx in (".dim", ".means", ".stds", ".modes"):
-            _same(stem + sfx, theirs + sfx)
+            assert open(stem + sfx, "rb").read() == z[f"chain_prep/out{sfx}"].tobytes(), sfx
     means = np.loadtxt(stem + ".means", dtype=np.float32)
     stds = np.loadtxt(stem + ".stds", dtype=np.float32)
     assert means.shape == (m,) and np.all(stds > 0)

@@ -2,8 +2,8 @@
 # 1. plain bench line; 2. rocprofv3 --kernel-trace --stats; 3. PMC passes (separate runs): FETCH_SIZE | WRITE_SIZE | SQ set
 TAG=${1:-r01}; R=$PWD; O=$R/gpurun_out/$TAG; rm -rf $O; mkdir -p $O
 python3 -c "import torch" > /dev/null 2>&1
-timeout -k 10 600 python3 bench.py --steps 20 --warmup 3 > $O/bench.log 2>&1 && grep '^{' $O/bench.log > $O/${TAG}_bench.json
-(cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-chromosome > $O/trace.log 2>&1)
+timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 3 > $O/bench.log 2>&1 && grep '^{' $O/bench.log > $O/${TAG}_bench.json
+(cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-chromosome > $O/trace.log 2>&1)
 cp $(find $O/trace -name '*kernel_stats.csv' | head -1) $O/${TAG}_bench_kernel_stats.csv
 # the same trace, per kernel and GRID: a kernel that also runs on the small problems of the process (parity run of the
 # oracle-sized block, second stages of the end-to-end block) averages over unlike launches in the stats file above
@@ -18,15 +18,15 @@ for (kn, g, w), (c, t) in sorted(acc.items(), key=lambda kv: -kv[1][1]):
     print(f'"{kn}",{g},{w},{c},{int(t)},{t / c:.1f}')
 PY
 # the hetcor engine on the same block (bench.py --engine cuskss): bench line + kernel stats
-timeout -k 10 600 python3 bench.py --engine cuskss --steps 20 --warmup 3 --no-chromosome > $O/bench_cuskss.log 2>&1 && grep '^{' $O/bench_cuskss.log > $O/${TAG}_bench_cuskss.json
-(cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_ss -o t -- python3 $R/bench.py --engine cuskss --steps 20 --warmup 3 --no-cpu-baseline --no-chromosome > $O/trace_ss.log 2>&1)
+timeout -k 10 600 python3 bench.py --full --engine cuskss --steps 20 --warmup 3 --no-chromosome > $O/bench_cuskss.log 2>&1 && grep '^{' $O/bench_cuskss.log > $O/${TAG}_bench_cuskss.json
+(cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_ss -o t -- python3 $R/bench.py --full --engine cuskss --steps 20 --warmup 3 --no-cpu-baseline --no-chromosome > $O/trace_ss.log 2>&1)
 cp $(find $O/trace_ss -name '*kernel_stats.csv' | head -1) $O/${TAG}_bench_cuskss_kernel_stats.csv
 # whole-chromosome job (the `scale` leg): kernel stats of the batched block driver alone
-(cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_chrom -o t -- python3 $R/bench.py --workload chromosome --steps 5 --warmup 1 > $O/trace_chrom.log 2>&1)
+(cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_chrom -o t -- python3 $R/bench.py --full --workload chromosome --steps 5 --warmup 1 > $O/trace_chrom.log 2>&1)
 cp $(find $O/trace_chrom -name '*kernel_stats.csv' | head -1) $O/${TAG}_chromosome_kernel_stats.csv
 grep '^{' $O/trace_chrom.log > $O/${TAG}_chromosome_bench.json
 # kernel timeline of one headline step
-(cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o r -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-chromosome > $O/p.log 2>&1); python3 tools/timeline.py $O/prof/r_results.db > $O/${TAG}_timeline.txt
+(cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o r -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-chromosome > $O/p.log 2>&1); python3 tools/timeline.py $O/prof/r_results.db > $O/${TAG}_timeline.txt
 # the sepselect path: kernel stats of one timing run, JSON line of the tool beside it
 (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ss -o s -- python3 $R/tests/perf_sepselect.py --traits 80 --markers 8000 --sample-pairs 20 > $O/ss.log 2>&1)
 cp $(find $O/ss -name '*kernel_stats.csv' | head -1) $O/${TAG}_sepselect_kernel_stats.csv
@@ -34,7 +34,7 @@ grep '^{' $O/ss.log > $O/${TAG}_sepselect.json
 i=0
 for G in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --pmc $G --kernel-trace --output-format csv -d $O/pmc$i -o r -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-chromosome > $O/pmc$i.log 2>&1)
+  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --pmc $G --kernel-trace --output-format csv -d $O/pmc$i -o r -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-chromosome > $O/pmc$i.log 2>&1)
 done
 python3 - "$O" "$TAG" <<'PY'
 import csv, glob, sys, collections, json
@@ -56,7 +56,7 @@ for r in rows:
     k = (kn, r["Counter_Name"])
     acc[k][0] += float(r["Counter_Value"]); acc[k][1] += 1
 with open(f"{O}/{TAG}_pmc_summary.txt", "w") as out:
-    out.write("rocprofv3 --pmc <set> --kernel-trace -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-chromosome  (MI355X, three separate passes:\n"
+    out.write("rocprofv3 --pmc <set> --kernel-trace -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-chromosome  (MI355X, three separate passes:\n"
               "FETCH_SIZE | WRITE_SIZE | SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE)\n"
               "per-launch averages over the launches with the kernel's largest grid (the headline block); FETCH_SIZE / WRITE_SIZE in KiB as rocprofv3 reports them\n\n")
     last = None
