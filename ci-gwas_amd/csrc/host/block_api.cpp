@@ -464,6 +464,12 @@ extern "C" int cusk_merge_packed(const char *blockfile, const void *buf, size_t 
     return CUSK_OK;
 }
 
+extern "C" int cusk_count_significant(const float *mxp, size_t count, float th0)
+{
+    if (!mxp && count) return -1;
+    return count_significant(mxp, count, th0);
+}
+
 extern "C" int cusk_packed_results_write(const void *buf, size_t bytes, const char *outdir, int *blocks_written)
 {
     if ((!buf && bytes) || !outdir) return CUSK_ERR_ARG;

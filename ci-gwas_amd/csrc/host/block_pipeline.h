@@ -113,12 +113,17 @@ inline std::vector<int> subset_variables_depth1(const Bits &traits, int num_var,
     return out;
 }
 
-// cli.cpp:561-565: how many marker-trait correlations have |atanh c| >= th0.  That is a comparison of |c| with tanh(th0):
-// only the elements within 1e-6 (relative) of that value, NaN and |c| >= 1 go through the reference's expression -- its
-// two double-precision logs per element cost 0.7 ms on the 200,000 correlations of a 10k-SNP x 20-trait block.
+// cli.cpp:561-565: how many marker-trait correlations have |atanh c| >= th0.  That is a comparison of |c| with t = tanh(th0):
+// only the elements near t, NaN and |c| >= 1 go through the reference's expression -- its two logs per element cost 0.7 ms
+// on the 200,000 correlations of a 10k-SNP x 20-trait block.  The expression works in float (<math.h> gives the float
+// overloads): rounding 1 + c and 1 - c (2^-24 relative each) moves z = 0.5 (log - log) by up to 2^-24, the float logs and
+// their difference add a few ulp of z, and |dc| = (1 - c^2) |dz| stays below 2^-22 + 1e-6 |c|.  That is absolute, not
+// relative to t: at th0 = 0.0055 (N = 500k) it is 1e-5 of t, ten times the 1e-6 band this used to have.  The band is
+// 2^-20 + 1e-5 t, four times both terms.
 inline int count_significant(const float *mxp, size_t count, float th0)
 {
-    const double c_lo = std::tanh((double)th0) * (1.0 - 1e-6), c_hi = std::tanh((double)th0) * (1.0 + 1e-6);
+    const double t = std::tanh((double)th0), band = 0x1p-20 + 1e-5 * t;
+    const double c_lo = t - band, c_hi = t + band;
     int num_sig = 0;
     for (size_t i = 0; i < count; i++)
     {

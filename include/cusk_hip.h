@@ -389,6 +389,9 @@ int cusk_packed_results_write(const void *buf, size_t bytes, const char *outdir,
  * cusk_packed_results_write and cusk_merge_packed (not by the reference-side Python unpacker: use it between library calls). */
 size_t cusk_batch_result_packed_bytes_ex(const cusk_batch_result *r, int with_sep);
 int cusk_batch_result_pack_ex(const cusk_batch_result *r, void *buf, size_t bytes, int with_sep);
+/* host only: how many of the count marker-trait correlations pass the reference's pre-filter |atanh(c)| >= th0 (cli.cpp:561-565,
+ * in that expression's float arithmetic) -- the num_sig of cusk_block_stats, 0 skips a block; -1 if mxp is NULL */
+int cusk_count_significant(const float *mxp, size_t count, float th0);
 /* `merge-block-outputs` (cusk_postprocessing/merge_blocks.py:361-395 + write_mm :298-325) on the packed results of a whole
  * job, in memory: writes <basepath>_sam.mtx, <basepath>_scm.mtx, <basepath>.mdim, <basepath>.ixs -- the files the
  * reference's merge writes from the per-block files, byte for byte.  blockfile = the job's .blocks file (order of the

@@ -1216,3 +1216,15 @@ int orc_block_chr(const float *v, int n, int max_block_size, long long *first, l
     return nb;
 }
 
+
+/* cli.cpp:561-565, one verdict per element: |0.5 (log|1 + c| - log|1 - c|)| >= Th[0].  cli.cpp includes <math.h>, whose
+ * C++ form declares the float overloads of log and fabs, so with a float c the two sums, both logs and their difference
+ * are single precision; only the scaling by 0.5 and the comparison are double. */
+void orc_prefilter_flags(const float *mxp, size_t count, float th0, int32_t *out)
+{
+    for (size_t i = 0; i < count; i++) {
+        const float c = mxp[i];
+        const float d = logf(fabsf(1.0f + c)) - logf(fabsf(1.0f - c));
+        out[i] = fabs(0.5 * (double)d) >= (double)th0;
+    }
+}

@@ -66,6 +66,7 @@ def lib():
         L.orc_npn_from_counts.restype = C.c_float
         L.orc_npn_from_counts.argtypes = [f32p]
         L.orc_marker_corr_banded.argtypes = [u8p, C.c_size_t, C.c_size_t, C.c_size_t, f32p]
+        L.orc_prefilter_flags.argtypes = [f32p, C.c_size_t, C.c_float, i32p]
         L.orc_banded_row_abs_sums.argtypes = [f32p, C.c_size_t, C.c_size_t, f32p]
         L.orc_hanning_smoothing.argtypes = [f32p, C.c_int, C.c_int, np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")]
         L.orc_block_chr.argtypes = [f32p, C.c_int, C.c_int, i64p, i64p, C.c_int]
@@ -215,12 +216,17 @@ def square_from_cusk_corrs(mxm, mxp, pxp, m: int, p: int) -> np.ndarray:
     return sq
 
 
+def prefilter_flags(mxp, th0: float) -> np.ndarray:
+    """src/cli.cpp:561-565 per element: |atanh(r)| >= Th[0] in the expression's own arithmetic (float sums and logs)."""
+    c = np.ascontiguousarray(mxp, np.float32).reshape(-1)
+    out = np.zeros(c.size, np.int32)
+    lib().orc_prefilter_flags(c, c.size, float(np.float32(th0)), out)
+    return out.astype(bool)
+
+
 def prefilter_count(mxp, th0: float) -> int:
-    """src/cli.cpp:561-565: number of |atanh(r)| >= Th[0] (double arithmetic on float r)."""
-    c = np.asarray(mxp, np.float32)
-    one = np.float32(1)
-    z = np.abs(0.5 * (np.log(np.abs((one + c)).astype(np.float64)) - np.log(np.abs(one - c).astype(np.float64))))
-    return int(np.sum(z >= np.float64(np.float32(th0))))
+    """src/cli.cpp:561-565: number of marker-trait correlations with |atanh(r)| >= Th[0]."""
+    return int(np.count_nonzero(prefilter_flags(mxp, th0)))
 
 
 # --------------------------------------------------------------------------

@@ -217,8 +217,24 @@ def test_level0_guard_band_and_unusual_values(cg, eng, oracle, n):
     settles |c| against tanh(th) outside a guard band and leaves the band, |c| > 1 (where 0.5 |log |(1+c)/(1-c)|| comes
     back down: c = 100 is "independent") and NaN to the reference's arithmetic.  n covers border-only tilings (257) and
     tilings with interior tiles (700, 1100), whose code path carries no index clamps."""
+    _level0_guard_band(cg, eng, oracle, n, 1000, 0.01)
+
+
+# Th[0] at biobank sample sizes: 0.0055 (N = 500k), 0.0028 (2M) and 0.0012 (10M), the last below kThMinFilter = 2e-3
+# (sweep_common.h), where level 0 has no fast range and decides every element exactly
+BIOBANK_TH = [(500_000, 1e-4), (2_000_000, 1e-4), (10_000_000, 1e-4)]
+
+
+@pytest.mark.parametrize("N,alpha", BIOBANK_TH)
+@pytest.mark.parametrize("n", [257, 700, 1100])
+def test_level0_guard_band_at_biobank_thresholds(cg, eng, oracle, n, N, alpha):
+    """the test above with the thresholds of 500k to 10M individuals"""
+    _level0_guard_band(cg, eng, oracle, n, N, alpha)
+
+
+def _level0_guard_band(cg, eng, oracle, n, N, alpha):
     rng = np.random.default_rng(n)
-    Th = cg.threshold_array(1000, 0.01)
+    Th = cg.threshold_array(N, alpha)
     t = float(np.tanh(Th[0]))
     Cm = rng.uniform(-0.3, 0.3, (n, n)).astype(np.float32)
     iu = np.triu_indices(n, 1)
@@ -286,6 +302,115 @@ def test_fast_filter_never_contradicts_exact_path(cg, oracle, synth, mode):
         assert sum(st.rechecks) < 0.05 * max(1, sum(st.tests[2:])) + 1000
         Cd.free()
     e.close()
+
+
+def test_hetcor_level0_per_pair_switch_to_exact(cg, eng, oracle):
+    """hetcor level 0 with a per-pair sample size that straddles the switch to exact evaluation inside one matrix: a pair
+    takes the single-precision estimate only while th / sqrt(ess - 3) >= kThMinFilter = 2e-3 (ess below ~3.8M at
+    alpha = 1e-4), every other pair goes to the reference's double-precision threshold; elements crowd each pair's own
+    boundary tanh(th / sqrt(ess - 3))."""
+    n = 300
+    rng = np.random.default_rng(29)
+    th = cg.hetcor_threshold(1e-4)
+    Nm = np.exp(rng.uniform(np.log(1e6), np.log(1.5e7), (n, n))).astype(np.float32)
+    Nm = np.ascontiguousarray(np.triu(Nm, 1) + np.triu(Nm, 1).T + np.diag(np.diag(Nm)))
+    lth = th / np.sqrt(Nm.astype(np.float64) - 3)
+    iu = np.triu_indices(n, 1)
+    assert (lth[iu] >= 2e-3).mean() > 0.2 and (lth[iu] < 2e-3).mean() > 0.2
+    bnd = np.tanh(lth[iu])
+    v = rng.uniform(-0.01, 0.01, len(iu[0]))
+    near = rng.random(len(v)) < 0.5
+    v[near] = bnd[near] * (1 + rng.uniform(-2e-3, 2e-3, near.sum())) * rng.choice([-1, 1], near.sum())
+    ulp = rng.choice(len(v), 600, replace=False)
+    v[ulp] = bnd[ulp] * (1 + rng.integers(-8, 9, 600) * 2.0 ** -23)
+    Cm = np.eye(n, dtype=np.float32)
+    Cm[iu] = v.astype(np.float32)
+    Cm.T[iu] = Cm[iu]
+    ref = oracle.hetcor_skeleton(Cm, np.ones((n, n), np.int32), Nm, th, 0, np.zeros(n, np.int32))
+    Cd, Nd = cg.DeviceArray(Cm), cg.DeviceArray(Nm)
+    st = eng.run_hetcor(Cd.ptr, n, th, 0, N_dev=Nd.ptr)
+    G = eng.adjacency()
+    Cd.free()
+    Nd.free()
+    assert st.level == ref.level
+    assert np.array_equal(G, ref.G)
+    kept = G[iu] == 1
+    assert 0.2 < kept.mean() < 0.8
+    assert kept[lth[iu] >= 2e-3].any() and (~kept[lth[iu] < 2e-3]).any()
+
+
+def _biobank_corr(synth, N, seed, m=150, p=6):
+    """a correlation block with the sampling noise of N individuals.  Up to 500k: synth_corr_block (genotypes and traits
+    drawn, then correlated).  Beyond that: the population correlation of a sparse linear SEM (a few strong edges that build
+    the structure of the deeper levels, many of a few / sqrt(N) that land near the thresholds) plus symmetric Gaussian
+    noise of 1 / sqrt(N), far below the smallest eigenvalue, so the matrix stays positive definite."""
+    if N <= 500_000:
+        return synth.synth_corr_block(m, p, N=N, block_index=seed)
+    n = m + p
+    rng = np.random.default_rng(seed)
+    B = np.tril(rng.random((n, n)) < 10.0 / n, -1).astype(np.float64)
+    strong = rng.random((n, n)) < 0.3
+    B *= np.where(strong, rng.uniform(0.1, 0.3, (n, n)), rng.uniform(1.0, 8.0, (n, n)) / np.sqrt(N))
+    B *= rng.choice([-1.0, 1.0], (n, n))
+    A = np.linalg.inv(np.eye(n) - B)
+    S = A @ A.T
+    d = np.sqrt(np.diag(S))
+    Cm = S / np.outer(d, d)
+    E = rng.normal(0, 1 / np.sqrt(N), (n, n))
+    Cm = Cm + np.triu(E, 1) + np.triu(E, 1).T
+    np.fill_diagonal(Cm, 1.0)
+    assert np.linalg.eigvalsh(Cm).min() > 0
+    return np.ascontiguousarray(Cm, np.float32)
+
+
+@pytest.mark.parametrize("N,alpha", BIOBANK_TH)
+@pytest.mark.parametrize("mode", ["skeleton", "hetcor", "het"])
+def test_fast_filter_at_biobank_thresholds(cg, oracle, synth, mode, N, alpha):
+    """levels >= 1 with the thresholds of 500k to 10M individuals on matrices whose noise matches N, so that many tests
+    of every level land near t: the certified cut-offs (level1_beta, kBeta of ci_fast.h, hetcor's per-pair switch) are
+    never contradicted by the exact path, the answer equals the oracle's and the exact-only engine's, and the bands are
+    populated wherever the thresholds are large enough to have them (>= kThMinFilter = 2e-3).  The recheck-ratio bar of
+    the test above is not carried over: small thresholds legitimately recheck more."""
+    ml = 5
+    Cm = _biobank_corr(synth, N, seed=41 + N % 97)
+    n = Cm.shape[0]
+    e = cg.Engine(0)
+    e.set_option("validate", 1)
+    Cd = cg.DeviceArray(Cm)
+    rng = np.random.default_rng(5)
+    if mode == "skeleton":
+        Th = cg.threshold_array(N, alpha)
+        st = e.run_skeleton(Cd.ptr, n, Th, ml)
+        G = e.adjacency()
+        ref = oracle.skeleton(Cm, Th, ml)
+        x, y, lv, z, S = e.sepsets()
+        assert np.array_equal(_dense_sepsets(n, x, y, S), ref.sepset)
+        e.set_option("fast", 0)
+        st0 = e.run_skeleton(Cd.ptr, n, Th, ml)
+        filtered = Th[1] >= 2e-3
+    else:
+        th = cg.hetcor_threshold(alpha)
+        Nm = np.full((n, n), N, np.float32)
+        if mode == "het":
+            Nm = (Nm * rng.uniform(0.6, 1.0, (n, n))).astype(np.float32)
+            Nm = np.maximum(Nm, Nm.T)
+        Nd = cg.DeviceArray(Nm)
+        kw = dict(N_dev=Nd.ptr if mode == "het" else None, ess_uniform=float(N))
+        st = e.run_hetcor(Cd.ptr, n, th, ml, **kw)
+        G = e.adjacency()
+        ref = oracle.hetcor_skeleton(Cm, np.ones((n, n), np.int32), Nm, th, ml, np.zeros(n, np.int32))
+        e.set_option("fast", 0)
+        st0 = e.run_hetcor(Cd.ptr, n, th, ml, **kw)
+        Nd.free()
+        filtered = th / np.sqrt(float(Nm.min()) - 3 - ml) >= 2e-3
+    assert np.array_equal(e.adjacency(), G) and st0.level == st.level
+    Cd.free()
+    e.close()
+    assert st.violations == 0 and st.exact_fallbacks == 0
+    assert np.array_equal(G, ref.G) and st.level == ref.level
+    assert st.level >= 2 and sum(st.tests[2:]) > 0
+    if filtered:  # level 1 settles its band inside the kernel (no queue, no counter); the deeper levels queue theirs
+        assert any(r > 0 for r in st.rechecks[2:]), list(st.rechecks)
 
 
 def test_asymmetric_matrix_and_generic_level1(cg, eng, oracle, synth):
