@@ -452,3 +452,219 @@ def rand_dag_corr(snp: int = 500, tr: int = 5, nl: int = 2, n: int = 16000, deg:
     if return_dag:
         return Cm, G, A
     return Cm
+
+
+# ---------------------------------------------------------------- inputs that steer the level sweep's dispatch
+# Ranks of conditioning sets at the work-item boundaries of the sweep kernels: k * 64 - 1, k * 64, k * 64 + 1 for the
+# small items (chunk0 = chunk0_low = 64), and the same around 256, 512 and 2048 (chunk = 256 and the default items).
+DISPATCH_RANKS = (63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 2047, 2048, 2049)
+
+
+def comb_rank(pos, d: int) -> int:
+    """0-based lexicographic rank of the ascending positions `pos` among the l-subsets of range(d): the order in which
+    the level sweep enumerates the conditioning sets of a row with d neighbours (rank r is the reference's r + 1)."""
+    from math import comb
+
+    l, r, prev = len(pos), 0, -1
+    for i, p in enumerate(pos):
+        for v in range(prev + 1, p):
+            r += comb(d - 1 - v, l - 1 - i)
+        prev = p
+    return r
+
+
+def comb_unrank(r: int, d: int, l: int) -> list:
+    """inverse of comb_rank"""
+    from math import comb
+
+    out, v = [], 0
+    for i in range(l):
+        while r >= comb(d - 1 - v, l - 1 - i):
+            r -= comb(d - 1 - v, l - 1 - i)
+            v += 1
+        out.append(v)
+        v += 1
+    return out
+
+
+def _partial_z(A: np.ndarray, x: int, y: int, S) -> float:
+    """|atanh| of the partial correlation of x and y given S, in float64, for variables that are rows of A over
+    independent unit innovations (covariance A A^T)"""
+    idx = [x, y] + list(S)
+    M = A[idx] @ A[idx].T
+    P = np.linalg.inv(M)
+    return abs(float(np.arctanh(-P[0, 1] / np.sqrt(P[0, 0] * P[1, 1]))))
+
+
+def _bisect(f, lo: float, hi: float, target: float, it: int = 60) -> float:
+    """f increasing on [lo, hi]: the argument where f crosses target"""
+    for _ in range(it):
+        mid = 0.5 * (lo + hi)
+        if f(mid) < target:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
+def dispatch_case(degrees, level: int, seed: int, N: int = 2_000_000, alpha: float = 1e-4, ranks=DISPATCH_RANKS,
+                  max_twins: int = 2):
+    """Population correlation matrix (float32) of independent hub blocks that reach level `level` with one hub row of
+    each degree in `degrees`, and what the sweep of that level must find.
+
+    A hub H is a signed combination of its "sources" (independent variables) plus noise; its neighbour list at level l
+    is positions 0..d-1 in variable order.  "Hangers" V = sum_{t in T} sign(w_t) X_t + 5 e sit at free positions of that
+    list: V stays adjacent to H below level |T| = l and is separated from it by T exactly, which sits at rank r of H's
+    list.  Every target rank in `ranks` below C(d, l) gets one hanger.  Up to `max_twins` of them get a second passing
+    set in a later work item: one member t of T gets a near copy X_p = X_t + sigma e at a free position p whose set
+    T - t + p has a rank in a later 64-set item; sigma is tuned so that set's z is about th / 2.  Two more hangers per
+    hub carry a weak extra path gamma X_c whose z given T is tuned to th (1 -+ 2.5e-4): inside the guard band of the
+    fast filters (+-1e-3 relative on |rho|), one just passing and one just failing.  One hanger per level below l
+    (random sources) thins the hub's list on the way.
+
+    Returns (Cm, info): info["hubs"] is a list with, per hub, its index "h", degree "d", the variable index of every
+    list position "pos" (ascending), "targets" (variable index of V, rank, T as variable indices), "twins" (V, rank of
+    the second set, that set), "near" (V, T, passes), and info["th"] is the level's Fisher-z threshold."""
+    from math import comb
+    from statistics import NormalDist
+
+    rng = np.random.default_rng(seed)
+    th = NormalDist().inv_cdf(1.0 - alpha / 2.0) / np.sqrt(N - level - 3.0)
+    l = level
+    blocks = []  # per hub: the roles of its list positions
+    for d in degrees:
+        targets = [(r, comb_unrank(r, d, l)) for r in ranks if r < comb(d, l)]
+        while True:  # small rows: as many targets as leave room for their hangers (and the near copies)
+            used = set()
+            for _, T in targets:
+                used.update(T)
+            if len(used) + len(targets) + max_twins + 2 * (l + 2) <= d:
+                break
+            targets.pop()
+        # near copies: replace the largest member of T whose replacement whose replacement by a free position lands in a later 64-set item
+        twins = []
+        for r, T in targets:
+            if len(twins) >= max_twins:
+                break
+            best = None
+            for t in sorted(T, reverse=True):
+                for p in range(t + 1, d):
+                    if p in used or any(p == q for _, _, q in twins):
+                        continue
+                    T2 = sorted([v for v in T if v != t] + [p])
+                    r2 = comb_rank(T2, d)
+                    if r2 // 64 > r // 64:
+                        best = (r, t, p)
+                        break
+                if best:
+                    break
+            if best:
+                twins.append(best)
+                used.add(best[2])
+        free = [p for p in range(d) if p not in used]
+        rng.shuffle(free)
+        near = []
+        for passes in (True, False):
+            if len(free) < l + 1 + len(targets) + 3:
+                break
+            T = sorted(free[:l])
+            c = free[l]
+            free = free[l + 1:]
+            near.append((T, c, passes))
+        nhang = len(targets) + len(near)
+        if len(free) < nhang:
+            raise ValueError(f"degree {d} at level {l}: {nhang} hangers but {len(free)} free positions")
+        hang_pos = sorted(free[:nhang])
+        sources = [p for p in range(d) if p not in set(hang_pos)]
+        lower = []
+        plain = [p for p in sources if p not in used and p not in {q for T, c, _ in near for q in T + [c]}]
+        for l2 in range(1, l if len(plain) >= l else 1):
+            lower.append(sorted(rng.choice(plain, l2, replace=False).tolist()))
+        blocks.append(dict(d=d, targets=targets, twins=twins, near=near, hang_pos=hang_pos, sources=sources, lower=lower))
+
+    n = sum(b["d"] + len(b["lower"]) + 1 for b in blocks)
+    A = np.zeros((n, n))
+    hubs = []
+    base = 0
+    for b in blocks:
+        d = b["d"]
+        H = base + d + len(b["lower"])
+        idx = lambda p: base + p  # noqa: E731
+        twin_of = {p: t for _, t, p in b["twins"]}
+        for p in b["sources"]:
+            A[idx(p), idx(p)] = 1.0
+        for p, t in twin_of.items():
+            A[idx(p), idx(t)] = 1.0
+            A[idx(p), idx(p)] = 0.1  # sigma, tuned below
+        w = rng.uniform(0.8, 1.2, d) * rng.choice([-1.0, 1.0], d)
+        for p, t in twin_of.items():  # H - X_t | X_p ~ w_t sigma / sd(H) keeps both copies in H's list
+            w[p] = w[t]
+
+        def set_hub():
+            A[H] = 0.0
+            for p in b["sources"]:
+                A[H] += w[p] * A[idx(p)]
+            A[H, H] += 1.0
+
+        set_hub()
+        hang = iter(b["hang_pos"])
+        info = dict(h=H, d=d, pos=[idx(p) for p in range(d)], targets=[], twins=[], near=[])
+
+        def add_hanger(v, T):
+            A[v] = 0.0
+            for t in T:
+                A[v] += np.sign(w[t]) * A[idx(t)]  # (signs of H's: no path cancels another)
+            A[v, v] += 5.0  # a noisy proxy of its sources: conditioning on hangers attenuates H - X_t, never cancels it
+
+        vt = {}
+        for r, T in b["targets"]:
+            v = idx(next(hang))
+            add_hanger(v, T)
+            vt[r] = v
+            info["targets"].append((v, r, [idx(t) for t in T]))
+        near_pos = [idx(next(hang)) for _ in b["near"]]  # (the hub's row is final once the near copies are tuned)
+        for r, t, p in b["twins"]:
+            v = vt[r]
+            T2 = sorted([q for q in comb_unrank(r, d, l) if q != t] + [p])
+
+            def z_of(sigma):
+                A[idx(p), idx(p)] = sigma
+                set_hub()
+                return _partial_z(A, H, v, [idx(q) for q in T2])
+
+            z_of(_bisect(z_of, 1e-3, 1.0, 0.5 * th))
+            info["twins"].append((v, comb_rank(T2, d), [idx(q) for q in T2]))
+        for T, c, passes in b["near"]:
+            v = near_pos.pop(0)
+            add_hanger(v, T)
+            row = A[v].copy()
+            g = np.sign(w[c])
+
+            def z_of(gamma):
+                A[v] = row + gamma * g * A[idx(c)]
+                return _partial_z(A, H, v, [idx(t) for t in T])
+
+            gamma = _bisect(z_of, 0.0, 4.0, th * (1.0 - 2.5e-4 if passes else 1.0 + 2.5e-4))
+            z_of(gamma)
+            info["near"].append((v, [idx(t) for t in T], passes))
+        for k, T in enumerate(b["lower"]):
+            add_hanger(base + d + k, T)
+        hubs.append(info)
+        base = H + 1
+    S = A @ A.T
+    s = np.sqrt(np.diag(S))
+    Cm = S / np.outer(s, s)
+    Cm = (Cm + Cm.T) / 2
+    np.fill_diagonal(Cm, 1.0)
+    return np.ascontiguousarray(Cm, np.float32), dict(hubs=hubs, th=float(th), level=l, N=N, alpha=alpha)
+
+
+# (level, hub degrees at the start of that level): every degree class, each class boundary (39/40, 63/64, 127/128,
+# 191/192) at level 2, class 3 at level 3, class 2 at level 4, class 1 at level 5; the oracle's cost per hub row is
+# about C(d, l) (d - l) tests
+DISPATCH_CASES = {
+    "l2": (2, (39, 40, 63, 64, 127, 128, 191, 192)),
+    "l3": (3, (39, 40, 63, 64, 127, 128)),
+    "l4": (4, (39, 40, 63, 64)),
+    "l5": (5, (39, 40, 41)),
+}
