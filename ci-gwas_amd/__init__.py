@@ -17,5 +17,6 @@ from .skeleton import (  # noqa: F401
     cu_marker_phen_corr_pearson,
     hetcor_skeleton,
     hetcor_threshold,
+    sumstats_write,
     threshold_array,
 )

@@ -113,6 +113,10 @@ SYMBOLS = {
     "cusk_corr_build_batch_mxm": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "cusk_corr_build_begin": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp]),
     "cusk_corr_build_end": (_i, [_vp, _vp]),
+    "cusk_corr_build_indexed": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "cusk_pack_lower_tri": (_i, [_vp, _vp, _sz, _sz, _vp, _i]),
+    "cusk_nan_to_zero": (_i, [_vp, _vp, _sz]),
+    "cusk_sumstats_write": (_i, [C.c_char_p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, C.c_char_p, _sz]),
     "cusk_corr_timing": (None, [_vp, _vp]),
     "cusk_corr_banded": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "cusk_hanning_smooth": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),

@@ -7,6 +7,8 @@ positional / optional arguments, same range checks, same conversion to the posit
 the native `mps` program with literal 'NULL' for absent paths, `subprocess.run(check=True)`.
 `cuskss-het` and `cuskss-merged` (README.md:65,75 of the reference names them, its CLI does
 not define them) are aliases of `cuskss` that insist on the flags that select that mode.
+Two things the reference leaves to the user: `sumstats` writes the three correlation files of `cuskss` from a
+PLINK set and a .phen, and `cuskss-merged --bfiles --phen` runs the merged step straight from those.
 
 `sepselect` and `orient-v-structs` (ci-gwas.py:303-358, handlers :467-476) run this package's device-backed
 mirror of cusk_postprocessing/sepselect.py (ci-gwas_amd/sepselect.py) and write the same files.
@@ -84,9 +86,12 @@ def _add_block(sub):
 
 def _add_cuskss(sub, name, help_):
     p = sub.add_parser(name, help=help_)
+    # cuskss-merged alone can take the genotypes instead of the three correlation files (cuskss_bed_argv): there --pxp
+    # and --num-samples are asked for by cuskss_argv once it knows which route it is on
+    from_bed = name == "cuskss-merged"
     p.add_argument("--mxm", type=str, default="NULL")
     p.add_argument("--mxp", type=str, default="NULL")
-    p.add_argument("--pxp", type=str, required=True)
+    p.add_argument("--pxp", type=str, required=not from_bed, default="NULL")
     p.add_argument("--mxp-se", type=str, default="NULL")
     p.add_argument("--pxp-se", type=str, default="NULL")
     p.add_argument("--block-index", metavar="block-index", type=TypeCheck(int, "block-index", 0, None), default=0)
@@ -97,9 +102,25 @@ def _add_cuskss(sub, name, help_):
     p.add_argument("--max-level-two", metavar="max-level-two", type=TypeCheck(int, "max-level", 0, 14), default=14)
     p.add_argument("--max-depth", metavar="max-depth", type=TypeCheck(int, "max-depth", 1, None), default=1)
     p.add_argument("--time-index", type=str, default="NULL")
-    p.add_argument("--num-samples", metavar="num-samples", type=TypeCheck(int, "num-samples", 1, None), required=True)
+    p.add_argument("--num-samples", metavar="num-samples", type=TypeCheck(int, "num-samples", 1, None), required=not from_bed)
     p.add_argument("--outdir", type=str, default="./")
+    if from_bed:
+        p.add_argument("--bfiles", type=str, default=None,
+                       help="filestem of .bed, .bim, .fam fileset (after prep-bed): compute the correlations from the "
+                            "genotypes on the GPU instead of reading --mxm/--mxp/--pxp; needs --phen")
+        p.add_argument("--phen", type=str, default=None, help="path to standardized phenotype tsv (with --bfiles)")
     p.set_defaults(func=cuskss, variant=name)
+
+
+def _add_sumstats(sub):
+    p = sub.add_parser("sumstats", help="Compute the correlation files of cuskss (mxm.bin, mxp.txt, pxp.txt) from "
+                                        "genotypes and phenotypes (requires GPU)")
+    p.add_argument("bfiles", type=str, help="filestem of .bed, .bim, .fam fileset (after prep-bed)")
+    p.add_argument("phen", type=str, help="path to standardized phenotype tsv.")
+    p.add_argument("outdir", type=str)
+    p.add_argument("--marker-indices", metavar="marker-indices", type=str, default="NULL",
+                   help="markers whose LD is written to mxm.bin (merged_blocks.ixs of merge-block-outputs); default: all")
+    p.set_defaults(func=sumstats)
 
 
 def _add_merge(sub):
@@ -138,6 +159,7 @@ def build_parser() -> argparse.ArgumentParser:
     _add_cuskss(sub, "cuskss", "Infer skeleton using summary statistic data (requires GPU)")
     _add_cuskss(sub, "cuskss-het", "cuskss with heterogeneous (polychoric/polyserial) correlations: needs --mxp-se/--pxp-se")
     _add_cuskss(sub, "cuskss-merged", "cuskss on the union of markers selected in all blocks: needs --marker-indices")
+    _add_sumstats(sub)
     _add_merge(sub)
     _add_sepselect(sub)
     return parser
@@ -163,8 +185,50 @@ def cusk_argv(args) -> list[str]:
             str(args.max_level_two), str(args.max_depth), args.outdir, str(args.block_index)]
 
 
+def sumstats_argv(args) -> list[str]:
+    return [MPS_PATH, "sumstats", args.phen, args.bfiles, args.marker_indices, args.outdir]
+
+
+def sumstats(args):
+    subprocess.run(sumstats_argv(args), check=True)
+
+
+def cuskss_bed_argv(args) -> list[str]:
+    """`cuskss-merged --bfiles STEM --phen FILE`: the correlations of the selected markers and the traits are computed
+    from the genotypes and swept without leaving the GPU (`mps cuskss-bed`); same result files as the file route on
+    what `sumstats` writes"""
+    if args.bfiles is None or args.phen is None:
+        sys.exit("cuskss-merged: --bfiles and --phen go together.")
+    if any(v != "NULL" for v in (args.mxm, args.mxp, args.pxp)):
+        sys.exit("cuskss-merged: give either --bfiles/--phen or --mxm/--mxp/--pxp, not both.")
+    if args.mxp_se != "NULL" or args.pxp_se != "NULL":
+        sys.exit("cuskss-merged: --mxp-se/--pxp-se cannot be combined with --bfiles (Pearson correlations have no "
+                 "standard-error files).")
+    if args.blockfile != "NULL":
+        sys.exit("cuskss-merged: --blockfile does not apply with --bfiles.")
+    if args.marker_indices == "NULL":
+        sys.exit("cuskss-merged needs --marker-indices.")
+    if args.num_samples is not None:
+        try:
+            with open(args.bfiles + ".dim") as f:
+                in_dim = int(f.readline().split()[0])
+        except (OSError, ValueError, IndexError):
+            sys.exit(f"cuskss-merged: cannot read {args.bfiles}.dim (run prep-bed first).")
+        if in_dim != args.num_samples:
+            sys.exit(f"cuskss-merged: --num-samples {args.num_samples} differs from the {in_dim} individuals of "
+                     f"{args.bfiles}.dim.")
+    return [MPS_PATH, "cuskss-bed", args.phen, args.bfiles, args.marker_indices, args.time_index, str(args.alpha),
+            str(args.max_level_one), str(args.max_level_two), str(args.max_depth), args.outdir]
+
+
 def cuskss_argv(args) -> list[str]:
     """ci-gwas.py:423-451 (validation :424-429 included)"""
+    if getattr(args, "bfiles", None) is not None or getattr(args, "phen", None) is not None:
+        return cuskss_bed_argv(args)
+    if args.pxp == "NULL":
+        sys.exit("the following arguments are required: --pxp")
+    if args.num_samples is None:
+        sys.exit("the following arguments are required: --num-samples")
     if args.blockfile == "NULL" and args.marker_indices == "NULL":
         sys.exit("Either blockfile + block index or marker indices into the mxp file have to be provided for cuskss.")
     if sum([args.mxp_se == "NULL", args.pxp_se == "NULL"]) == 1:

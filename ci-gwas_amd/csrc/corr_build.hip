@@ -1286,7 +1286,7 @@ __global__ void extract_tri_kernel(const float *__restrict__ C, float *out, size
 }
 
 // true when p is a HIP device allocation (hipPointerGetAttributes fails for plain host memory: not an error here)
-static bool is_device_pointer(const void *p)
+bool is_device_pointer(const void *p)
 {
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, p) != hipSuccess)

@@ -198,6 +198,7 @@ float hetcor_threshold_host(float alpha);
 int corr_build_impl(cusk_engine *e, const unsigned char *bed, const float *phen, size_t m, size_t N,
                     size_t p, const float *mean, const float *std, float *C_dev, float *mxp_host,
                     float *mxm_tri_host, float *pxp_tri_host, bool ahead = false);
+bool is_device_pointer(const void *p);  // a HIP device allocation (or a pointer into one)
 
 // reference-named correlation entry points (corr_build.hip); C linkage in compat_api.hip, C++ linkage in compat_cxx.cpp
 void compat_marker_phen_corr_pearson(const unsigned char *marker_vals, const float *phen_vals, const size_t num_markers,

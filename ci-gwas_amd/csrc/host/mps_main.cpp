@@ -6,6 +6,9 @@
 //   mps cusk   <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index>
 //   mps cuskss <mxm> <mxp> <mxp_se> <pxp> <pxp_se> <time_index> <block_index> <blockfile>
 //              <marker_indices> <alpha> <l1> <l2> <depth> <num_samples> <outdir>   ("NULL" = absent)
+// and two commands the reference does not have, for users who hold the genotypes (see SUMSTATS_USAGE):
+//   mps sumstats   <.phen> <bfiles> <marker-indices|NULL> <outdir>
+//   mps cuskss-bed <.phen> <bfiles> <marker-indices> <time_index|NULL> <alpha> <l1> <l2> <depth> <outdir>
 // Differences by design: the correlation matrix never leaves HBM between the build and the
 // sweep, adjacency comes back as a bitmap, separating sets as sparse records, only the
 // retained sub-matrix is gathered to the host, and files are written with one fwrite each.
@@ -132,14 +135,17 @@ struct GC
     size_t num_markers() const { return num_var - num_phen; }
 };
 
-// run_cusk, cli.cpp:29-60: hetcor_skeleton, prune to depth, extract the retained sub-matrices
+// run_cusk, cli.cpp:29-60: hetcor_skeleton, prune to depth, extract the retained sub-matrices.  C_resident: the
+// num_var^2 matrix where a correlation build left it in HBM (gc.C is empty then); otherwise gc.C is uploaded.
 GC run_cusk(cusk_engine *e, const GC &gc, float th, float ess_uniform, bool het, int depth, int max_level,
-            const std::vector<int> &time_index_traits)
+            const std::vector<int> &time_index_traits, const float *C_resident = nullptr)
 {
     const int n = (int)gc.num_var;
     std::vector<int> ti(n, 0);
     for (size_t i = gc.num_markers(), r = 0; i < gc.num_var; i++, r++) ti[i] = time_index_traits[r];
-    DevMat C(gc.C);
+    std::unique_ptr<DevMat> uploaded;
+    if (!C_resident) uploaded.reset(new DevMat(gc.C));
+    const float *Cd = C_resident ? C_resident : uploaded->p;
     std::unique_ptr<DevMat> Nd;
     if (het) Nd.reset(new DevMat(gc.ess));
     int *Gd = nullptr;
@@ -149,7 +155,7 @@ GC run_cusk(cusk_engine *e, const GC &gc, float th, float ess_uniform, bool het,
         if (!Gd || cusk_dev_upload(Gd, gc.G.data(), sizeof(int) * gc.G.size()) != CUSK_OK) engine_die("upload G", e);
     }
     cusk_stats st;
-    if (cusk_run_hetcor(e, C.p, het ? Nd->p : nullptr, ess_uniform, Gd, n, th, max_level, ti.data(), &st) != CUSK_OK)
+    if (cusk_run_hetcor(e, Cd, het ? Nd->p : nullptr, ess_uniform, Gd, n, th, max_level, ti.data(), &st) != CUSK_OK)
         engine_die("hetcor_skeleton", e);
     cusk_dev_free(Gd);
     Bits G = fetch_adjacency(e);
@@ -159,7 +165,7 @@ GC run_cusk(cusk_engine *e, const GC &gc, float th, float ess_uniform, bool het,
     out.num_phen = gc.num_phen;
     out.new_to_old = compose(P, &gc.new_to_old);
     out.G = gather_adj(G, P);
-    out.C = gather(e, C.p, n, P);
+    out.C = gather(e, Cd, n, P);
     if (het) out.ess = gather(e, Nd->p, n, P);
     return out;
 }
@@ -296,12 +302,268 @@ int cmd_cuskss(int argc, char **argv)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------
+// mps sumstats / mps cuskss-bed: the inputs of `cuskss` on the merged marker set, from genotypes.  The reference has
+// no such command: its cuskss reads mxm / mxp / pxp files (cli.cpp:194-346) and leaves making them to the user.
+// ---------------------------------------------------------------------------------------
+const char *SUMSTATS_USAGE = R"(
+Compute the summary statistics cuskss reads (mxm, mxp, pxp) from genotypes and phenotypes.
+
+usage: mps sumstats <.phen> <bfiles> <marker-indices|NULL> <outdir>
+
+arguments:
+    .phen           path to standardized phenotype tsv
+    bfiles          stem of .bed, .bim, .fam fileset (with the .dim, .means, .stds of mps prep)
+    marker-indices  ascending global marker indices (int32 binary, merged_blocks.ixs) whose LD goes to mxm; NULL = all
+    outdir          receives mxm.bin, mxp.txt (all markers), pxp.txt
+)";
+
+const char *CUSKSS_BED_USAGE = R"(
+Run cuskss on the markers selected in all blocks, with the correlations computed from genotypes on the device.
+
+usage: mps cuskss-bed <.phen> <bfiles> <marker-indices> <time_index|NULL> <alpha> <max_level_one> <max_level_two> <depth> <outdir>
+)";
+
+// .phen, the prep files and the marker selection; the arrays every kernel reads are copied to the device once
+struct GenoInputs
+{
+    Phen phen;
+    std::vector<std::string> trait_names, chr, snp, ref;
+    BedDims dims;
+    MappedFile bed;
+    std::vector<float> means, stds;
+    std::vector<int> ixs;
+    unsigned char *bed_d = nullptr;
+    float *phen_d = nullptr, *means_d = nullptr, *stds_d = nullptr;
+    size_t N() const { return dims.num_samples; }
+    size_t m() const { return dims.num_markers; }
+    size_t p() const { return phen.num_phen; }
+    size_t k() const { return ixs.size(); }
+    // the .bed rows where the kernels find them: HBM, or the file mapping when the device has no room for all of them
+    // (the same entry points take either)
+    const unsigned char *bed_rows() const { return bed_d ? bed_d : bed.data + 3; }
+
+    void load(const std::string &phen_path, const std::string &bfiles, const std::string &index_path, bool want_bim)
+    {
+        std::cout << "Checking paths" << std::endl;
+        for (const char *sfx : {".bed", ".dim", ".means", ".stds", ".bim"}) check_path(bfiles + sfx);
+        check_path(phen_path);
+        if (index_path != "NULL") check_path(index_path);
+        if (!bed_has_valid_magic(bfiles + ".bed")) die("unexpected magic number in bed file.");
+        phen = load_phen(phen_path);
+        {
+            std::ifstream f(phen_path);
+            std::string header;
+            std::getline(f, header);
+            const auto w = split_ws(header);
+            if (w.size() != phen.num_phen + 2) die("header and rows of the .phen file differ in width");
+            trait_names.assign(w.begin() + 2, w.end());
+        }
+        dims = read_dims(bfiles + ".dim");
+        if (phen.num_samples != dims.num_samples) die("different num samples in phen and dims");
+        std::cout << "Found " << phen.num_phen << " phenotypes" << std::endl;
+        if (phen.num_phen == 0 || m() == 0 || N() == 0) die("nothing to correlate");
+        means = read_floats_line_range(bfiles + ".means", 0, std::numeric_limits<size_t>::max());
+        stds = read_floats_line_range(bfiles + ".stds", 0, std::numeric_limits<size_t>::max());
+        if (means.size() != m() || stds.size() != m()) die("number of markers and number of means or stds differ");
+        bed.open(bfiles + ".bed");
+        if (bed.size < 3 + m() * dims.bytes_per_col()) die(".bed file is smaller than .dim says");
+        if (want_bim)
+        {  // columns 1, 2, 5 of the .bim: the `chr snp ref` columns of an mxp file
+            std::ifstream f(bfiles + ".bim");
+            std::string line;
+            while (std::getline(f, line))
+            {
+                const auto w = split_ws(line);
+                if (w.size() < 5) continue;
+                chr.push_back(w[0]);
+                snp.push_back(w[1]);
+                ref.push_back(w[4]);
+            }
+            if (chr.size() != m()) die("number of markers in .bim and .dim differ");
+        }
+        if (index_path == "NULL")
+        {
+            ixs.resize(m());
+            std::iota(ixs.begin(), ixs.end(), 0);
+        }
+        else
+        {
+            std::cout << "Loading marker indices" << std::endl;
+            ixs = read_binary<int>(index_path);
+            if (ixs.empty()) die("marker index file is empty");
+            for (size_t i = 0; i < ixs.size(); i++)
+                if (ixs[i] < 0 || (size_t)ixs[i] >= m() || (i > 0 && ixs[i] <= ixs[i - 1]))
+                    die("marker indices must be ascending, distinct and smaller than the number of markers");
+        }
+        if (k() + p() > (size_t)std::numeric_limits<int>::max() / 2) die("too many variables");
+    }
+
+    void stage(cusk_engine *e)
+    {
+        auto up = [&](const void *src, size_t bytes, const char *what) -> void * {
+            void *d = cusk_dev_alloc(bytes);
+            if (!d || cusk_dev_upload(d, src, bytes) != CUSK_OK) engine_die(what, e);
+            return d;
+        };
+        phen_d = static_cast<float *>(up(phen.data.data(), sizeof(float) * phen.data.size(), "upload phenotypes"));
+        means_d = static_cast<float *>(up(means.data(), sizeof(float) * means.size(), "upload means"));
+        stds_d = static_cast<float *>(up(stds.data(), sizeof(float) * stds.size(), "upload stds"));
+        const size_t bed_bytes = m() * dims.bytes_per_col();
+        bed_d = static_cast<unsigned char *>(cusk_dev_alloc(bed_bytes));
+        if (!bed_d)
+            std::cout << "The .bed (" << bed_bytes << " bytes) does not fit the device: reading it from the host" << std::endl;
+        else if (cusk_dev_upload(bed_d, bed.data + 3, bed_bytes) != CUSK_OK)
+            engine_die("upload .bed", e);
+    }
+
+    // n x n matrix (selected markers, then traits) built where the sweep reads it
+    void build_square(cusk_engine *e, float *C_dev)
+    {
+        if (cusk_corr_build_indexed(e, bed_rows(), phen_d, ixs.data(), k(), m(), N(), p(), means_d, stds_d, C_dev, nullptr) !=
+            CUSK_OK)
+            engine_die("correlation build", e);
+    }
+
+    ~GenoInputs()
+    {
+        cusk_dev_free(bed_d);
+        cusk_dev_free(phen_d);
+        cusk_dev_free(means_d);
+        cusk_dev_free(stds_d);
+    }
+};
+
+int cmd_sumstats(int argc, char **argv)
+{
+    if (argc < 6)
+    {
+        std::cout << SUMSTATS_USAGE << std::endl;
+        std::exit(1);
+    }
+    const std::string phen_path = argv[2], bfiles = argv[3], index_path = argv[4], outdir = argv[5];
+    PhaseTimer tm;
+    check_path(outdir);
+    GenoInputs in;
+    in.load(phen_path, bfiles, index_path, true);
+    tm.mark("load phen, dim, means, stds, bim, indices; map bed");
+    cusk_engine *e = nullptr;
+    if (cusk_engine_create(&e, 0, nullptr) != CUSK_OK) engine_die("engine create (is a HIP device visible?)", nullptr);
+    if (tm.on) cusk_engine_set_option(e, "hostprof", 1);
+    in.stage(e);
+    tm.mark("engine create + inputs to the device");
+    const size_t k = in.k(), p = in.p(), m = in.m(), n = k + p;
+
+    std::cout << "Computing correlations of " << k << " selected markers and " << p << " traits" << std::endl;
+    DevMat C(n * n);
+    in.build_square(e, C.p);
+    if (tm.on)
+    {
+        float ms4[4];
+        cusk_corr_timing(e, ms4);
+        std::cout << "[t] device: marker x marker " << ms4[1] << " ms, marker x trait + trait x trait " << ms4[2] << " ms" << std::endl;
+    }
+    tm.mark("indexed build (gather + mxm + mxp + pxp)");
+    std::vector<float> tri(k * (k + 1) / 2);
+    if (cusk_pack_lower_tri(e, C.p, n, k, tri.data(), 0) != CUSK_OK) engine_die("pack mxm", e);
+    tm.mark("pack lower triangle + copy to host");
+    std::vector<int> traits(p);
+    std::iota(traits.begin(), traits.end(), (int)k);
+    const std::vector<float> pxp = gather(e, C.p, (int)n, traits);
+
+    std::cout << "Computing marker-trait correlations of all " << m << " markers" << std::endl;
+    std::vector<float> mxp(m * p);
+    const size_t chunk = 16384, clb = in.dims.bytes_per_col();
+    for (size_t c0 = 0; c0 < m; c0 += chunk)
+    {
+        const size_t mc = std::min(chunk, m - c0);
+        if (cusk_corr_build(e, in.bed_rows() + c0 * clb, in.phen_d, mc, in.N(), p, in.means_d + c0, in.stds_d + c0, nullptr,
+                            &mxp[c0 * p]) != CUSK_OK)
+            engine_die("marker-trait correlations", e);
+    }
+    tm.mark("genome-wide mxp");
+
+    std::cout << "Writing mxm.bin, mxp.txt, pxp.txt" << std::endl;
+    auto cstrs = [](const std::vector<std::string> &v) {
+        std::vector<const char *> out(v.size());
+        for (size_t i = 0; i < v.size(); i++) out[i] = v[i].c_str();
+        return out;
+    };
+    const auto chr = cstrs(in.chr), snp = cstrs(in.snp), ref = cstrs(in.ref), names = cstrs(in.trait_names);
+    char err[512] = "";
+    if (cusk_sumstats_write(outdir.c_str(), tri.data(), k, mxp.data(), m, p, pxp.data(), chr.data(), snp.data(), ref.data(),
+                            names.data(), err, sizeof(err)) != CUSK_OK)
+        die(err);
+    tm.mark("write files");
+    cusk_engine_destroy(e);
+    std::cout << "Done." << std::endl;
+    return 0;
+}
+
+int cmd_cuskss_bed(int argc, char **argv)
+{
+    if (argc < 11)
+    {
+        std::cout << CUSKSS_BED_USAGE << std::endl;
+        std::exit(1);
+    }
+    const std::string phen_path = argv[2], bfiles = argv[3], index_path = argv[4], time_index_path = argv[5];
+    const float alpha = std::stof(argv[6]);
+    const int max_level_one = std::stoi(argv[7]), max_level_two = std::stoi(argv[8]), depth = std::stoi(argv[9]);
+    const std::string outdir = argv[10];
+    if (index_path == "NULL") die("cuskss-bed needs marker indices");
+    check_path(outdir);
+    const bool time_indexed = time_index_path != "NULL";
+    if (time_indexed) check_path(time_index_path);
+    GenoInputs in;
+    in.load(phen_path, bfiles, index_path, false);
+    const size_t k = in.k(), p = in.p(), n = k + p;
+    const float num_samples = (float)in.N();
+    std::vector<int> time_index_traits(p, 1);
+    if (time_indexed)
+    {
+        std::cout << "Loading time_indices" << std::endl;
+        time_index_traits = read_ints_lines(time_index_path);
+        if (time_index_traits.size() < p) die("time index file has fewer lines than traits");
+    }
+    const float th = cusk_hetcor_threshold(alpha);
+    cusk_engine *e = nullptr;
+    if (cusk_engine_create(&e, 0, nullptr) != CUSK_OK) engine_die("engine create (is a HIP device visible?)", nullptr);
+    in.stage(e);
+
+    std::cout << "Computing correlations of " << k << " selected markers and " << p << " traits" << std::endl;
+    GC gc;
+    gc.num_phen = p;
+    gc.num_var = n;
+    gc.new_to_old.resize(n);
+    std::iota(gc.new_to_old.begin(), gc.new_to_old.end(), 0);
+    {
+        DevMat C(n * n);
+        in.build_square(e, C.p);
+        // what the loaders of the three files do to a NaN correlation (host_io.h: load_mxm_into, load_mxp, load_pxp)
+        if (cusk_nan_to_zero(e, C.p, n * n) != CUSK_OK) engine_die("NaN -> 0", e);
+        std::cout << "Starting first cusk stage" << std::endl;
+        gc = run_cusk(e, gc, th, num_samples, false, depth, max_level_one, time_index_traits, C.p);
+    }
+    if (max_level_two > 0)
+    {
+        std::cout << "Starting second cusk stage" << std::endl;
+        gc = run_cusk(e, gc, th, num_samples, false, depth, max_level_two, time_index_traits);
+    }
+    std::cout << "Retained " << gc.num_markers() << " markers" << std::endl;
+    write_gc(gc, make_path(outdir, "cuskss_merged", ""));
+    cusk_engine_destroy(e);
+    return 0;
+}
+
 const char *MPS_USAGE = R"(
 usage: mps <command> [<args>]
 
 commands:
     cusk                    Run the skeleton search on a single block of block diagonal genomic covariance matrix
     cuskss                  Run the skeleton search on a block of markers and traits with pre-computed correlations.
+    sumstats                Compute the correlation files cuskss reads (mxm, mxp, pxp) from genotypes and phenotypes
+    cuskss-bed              cuskss on the merged marker selection with the correlations computed from genotypes
     block                   Tile the marker x marker correlation matrix of every chromosome into LD blocks
     prep                    Prepare input (PLINK) .bed file for cusk: .dim, .means, .stds, .modes
 )";
@@ -505,6 +767,8 @@ int main(int argc, char **argv)
     {
         if (cmd == "cusk") return cmd_cusk(argc, argv);
         if (cmd == "cuskss") return cmd_cuskss(argc, argv);
+        if (cmd == "sumstats") return cmd_sumstats(argc, argv);
+        if (cmd == "cuskss-bed") return cmd_cuskss_bed(argc, argv);
         if (cmd == "block") return cmd_block(argc, argv);
         if (cmd == "prep") return cmd_prep(argc, argv);
     }

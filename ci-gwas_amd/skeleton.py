@@ -79,6 +79,30 @@ def cu_corr_pearson_npn(bed, phen, m, N, p, means, stds):
     return mxm[: m * (m - 1) // 2], mxp[: m * p], pxp[: p * (p - 1) // 2]
 
 
+def sumstats_write(outdir: str, mxm_tri, mxp, pxp, chr_ids, snp_ids, ref_alleles, trait_names) -> None:
+    """cusk_sumstats_write (host only): <outdir>/mxm.bin, mxp.txt, pxp.txt from arrays -- mxm_tri the lower triangle
+    with diagonal of the selected markers' LD, mxp m_total x p for every marker of the .bim, pxp p x p"""
+    tri = np.ascontiguousarray(mxm_tri, np.float32).reshape(-1)
+    pxp = np.ascontiguousarray(pxp, np.float32)
+    p = pxp.shape[0]
+    mxp = np.ascontiguousarray(mxp, np.float32).reshape(-1, p)
+    m_total = mxp.shape[0]
+    k = int((np.sqrt(8.0 * tri.size + 1.0) - 1.0) / 2.0)
+    if k * (k + 1) // 2 != tri.size or pxp.shape != (p, p):
+        raise ValueError("mxm_tri must hold k (k + 1) / 2 values and pxp must be square")
+    if not (len(chr_ids) == len(snp_ids) == len(ref_alleles) == m_total) or len(trait_names) != p:
+        raise ValueError("one chr / snp / ref entry per mxp row and one name per trait are needed")
+
+    def strings(v):
+        return (C.c_char_p * len(v))(*[str(x).encode() for x in v])
+
+    err = C.create_string_buffer(512)
+    rc = lib().cusk_sumstats_write(str(outdir).encode(), _ptr(tri), k, _ptr(mxp), m_total, p, _ptr(pxp), strings(chr_ids),
+                                   strings(snp_ids), strings(ref_alleles), strings(trait_names), err, len(err))
+    if rc != 0:
+        raise RuntimeError(f"cusk_sumstats_write failed ({rc}): {err.value.decode()}")
+
+
 @dataclass
 class Stats:
     level: int
@@ -285,6 +309,45 @@ class Engine:
         mxp = np.zeros(m * p, np.float32) if want_mxp else None
         self._check(lib().cusk_corr_build(self.h, _ptr(bed), _ptr(phen), m, N, p, _ptr(means), _ptr(stds), C_dev, _ptr(mxp)))
         return mxp
+
+    def corr_build_indexed(self, bed, phen, marker_ix, m_total: int, N: int, p: int, means, stds, C_dev: int,
+                           want_mxp: bool = False):
+        """cusk_corr_build_indexed: the build of the markers `marker_ix` (ascending global indices) of a .bed of m_total
+        markers.  bed / means / stds: host arrays of ALL markers, or DeviceArray copies of them (then the rows are
+        gathered on the device); the matrix in C_dev has the selected markers in index order, then the traits"""
+        def arg(a, dtype):
+            if isinstance(a, DeviceArray):
+                return a, a.ptr
+            a = np.ascontiguousarray(a, dtype)
+            return a, _ptr(a)
+
+        bed, bed_p = arg(bed, np.uint8)
+        means, means_p = arg(means, np.float32)
+        stds, stds_p = arg(stds, np.float32)
+        phen = np.ascontiguousarray(phen, np.float32)
+        ix = np.ascontiguousarray(marker_ix, np.int32)
+        mxp = np.zeros(len(ix) * p, np.float32) if want_mxp else None
+        self._check(lib().cusk_corr_build_indexed(self.h, bed_p, _ptr(phen), _ptr(ix), len(ix), int(m_total), int(N), int(p),
+                                                  means_p, stds_p, C_dev, _ptr(mxp)))
+        return mxp
+
+    def pack_lower_tri(self, C_dev: int, n: int, k: int) -> np.ndarray:
+        """the leading k x k block of the n x n device matrix as the `mxm` file holds it: lower triangle with diagonal,
+        row-major, NaN -> 0 (cusk_pack_lower_tri)"""
+        out = np.empty(k * (k + 1) // 2, np.float32)
+        self._check(lib().cusk_pack_lower_tri(self.h, C_dev, int(n), int(k), _ptr(out), 0))
+        return out
+
+    def nan_to_zero(self, M_dev: int, count: int) -> None:
+        """NaN -> 0 in place on `count` floats of a device allocation (cusk_nan_to_zero); asynchronous on the engine's
+        stream: read the result with `download` or hand it to a run of this engine"""
+        self._check(lib().cusk_nan_to_zero(self.h, M_dev, int(count)))
+
+    def download(self, src_dev: int, dtype, shape) -> np.ndarray:
+        """device -> host copy ordered after the engine's work (cusk_engine_download)"""
+        out = np.empty(shape, dtype)
+        self._check(lib().cusk_engine_download(self.h, _ptr(out), src_dev, out.nbytes))
+        return out
 
     def corr_banded(self, bed, m: int, N: int, width: int, want_band: bool = False):
         """`mps block`'s device part for one chromosome: forward row sums of |banded Kendall-npn correlations|

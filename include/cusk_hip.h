@@ -257,6 +257,39 @@ int cusk_corr_build_batch_mxp(cusk_engine *e, const unsigned char *bed_dev, cons
 int cusk_corr_build_batch_mxm(cusk_engine *e, const unsigned char *bed_dev, const float *phen_dev, const float *mean_dev,
                               const float *std_dev, size_t N, size_t p, int nblk, const long long *first_marker,
                               const int *markers, const int *base, const unsigned char *keep, int n, float *C_dev);
+/* cusk_corr_build for k markers that are NOT contiguous in the .bed: the markers of the build are the rows
+ * marker_ix[0 .. k-1] (HOST array; ascending, distinct, < m_total) of a .bed of m_total markers -- the union of the markers
+ * all LD blocks selected (merged_blocks.ixs), scattered over every chromosome; the reference has no counterpart, its
+ * `cuskss` takes their LD from a file (cli.cpp:294-338).  mean / std are indexed by GLOBAL marker (m_total entries).  bed,
+ * mean and std may each be host memory or device-resident (cusk_blockset_stage's copies, any cusk_dev_alloc): resident
+ * rows are packed into contiguous engine scratch by a row-gather kernel, of host arrays only the selected rows are
+ * uploaded; the kernels of cusk_corr_build then run on the packed rows, so the n x n matrix (n = k + p, selected markers in
+ * index order, then traits) and mxp_host (k x p, may be NULL) are bit for bit those of cusk_corr_build on the k rows made
+ * contiguous by the caller.  C_dev = NULL: marker x trait correlations only. */
+int cusk_corr_build_indexed(cusk_engine *e, const unsigned char *bed, const float *phen, const int *marker_ix, size_t k,
+                            size_t m_total, size_t N, size_t p, const float *mean, const float *std, float *C_dev,
+                            float *mxp_host);
+/* The leading k x k block of the n x n device matrix C_dev in the layout of the `mxm` file of `cuskss`
+ * (marker_summary_stats.cpp:8-24): lower triangle INCLUDING the diagonal, row-major, k (k + 1) / 2 floats, NaN (a marker
+ * without variance) written as 0 -- what the readers of that file make of it.  out: host memory (out_on_device = 0) or a
+ * 16-byte aligned device buffer (1).  Returns when the result is there. */
+int cusk_pack_lower_tri(cusk_engine *e, const float *C_dev, size_t n, size_t k, float *out, int out_on_device);
+/* NaN -> 0 in place on `count` floats of a device allocation (M_dev 16-byte aligned): what the mxm / mxp / pxp loaders of
+ * `cuskss` do to the correlations they read, for a matrix that goes from cusk_corr_build* to cusk_run_hetcor without
+ * visiting a file.  Asynchronous on the engine's stream. */
+int cusk_nan_to_zero(cusk_engine *e, float *M_dev, size_t count);
+/* Host only (no device, no engine): writes the three summary-statistic files of `cuskss` from arrays --
+ *   <outdir>/mxm.bin  mxm_tri as it is, k (k + 1) / 2 floats (the layout of cusk_pack_lower_tri), NaN -> 0;
+ *   <outdir>/mxp.txt  header "chr snp ref <trait names>", then m_total rows "chr[i] snp[i] ref[i] v1 .. vp" from mxp
+ *                     (m_total x p row-major), one per marker of the whole .bim so that marker indices select rows;
+ *                     NaN is written as NA;
+ *   <outdir>/pxp.txt  header = trait names, then p rows "name v1 .. vp" from pxp_square (p x p row-major); NaN as nan
+ * with nine significant digits (%.9g), which the loaders (marker_trait_summary_stats.cpp:40-299,
+ * trait_summary_stats.cpp:5-169: text -> float32) read back bit for bit.  Every write and close is checked; on failure
+ * the message goes to err (may be NULL) and an error code is returned. */
+int cusk_sumstats_write(const char *outdir, const float *mxm_tri, size_t k, const float *mxp, size_t m_total, size_t p,
+                        const float *pxp_square, const char *const *chr, const char *const *snp, const char *const *ref,
+                        const char *const *trait_names, char *err, size_t err_len);
 /* timing of the last cusk_corr_build: [0] decode, [1] count GEMM, [2] mxp/pxp, [3] total (ms) */
 void cusk_corr_timing(const cusk_engine *e, float *ms4);
 
