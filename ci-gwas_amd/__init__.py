@@ -15,8 +15,11 @@ from .skeleton import (  # noqa: F401
     Stats,
     cu_corr_pearson_npn,
     cu_marker_phen_corr_pearson,
+    ess_from_se,
     hetcor_skeleton,
     hetcor_threshold,
+    se_from_count,
     sumstats_write,
+    sumstats_write_se,
     threshold_array,
 )

@@ -117,6 +117,10 @@ SYMBOLS = {
     "cusk_pack_lower_tri": (_i, [_vp, _vp, _sz, _sz, _vp, _i]),
     "cusk_nan_to_zero": (_i, [_vp, _vp, _sz]),
     "cusk_sumstats_write": (_i, [C.c_char_p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, C.c_char_p, _sz]),
+    "cusk_pair_counts": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),
+    "cusk_ess_from_se": (_f, [_f, _f]),
+    "cusk_se_from_count": (_f, [_f, _i]),
+    "cusk_sumstats_write_se": (_i, [C.c_char_p, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, C.c_char_p, _sz]),
     "cusk_corr_timing": (None, [_vp, _vp]),
     "cusk_corr_banded": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "cusk_hanning_smooth": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),

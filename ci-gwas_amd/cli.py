@@ -8,7 +8,9 @@ the native `mps` program with literal 'NULL' for absent paths, `subprocess.run(c
 `cuskss-het` and `cuskss-merged` (README.md:65,75 of the reference names them, its CLI does
 not define them) are aliases of `cuskss` that insist on the flags that select that mode.
 Two things the reference leaves to the user: `sumstats` writes the three correlation files of `cuskss` from a
-PLINK set and a .phen, and `cuskss-merged --bfiles --phen` runs the merged step straight from those.
+PLINK set and a .phen, and `cuskss-merged --bfiles --phen` runs the merged step straight from those.  For phenotypes
+with missing values `sumstats --se` adds the two standard-error files (from the number of individuals each pair was
+observed on) and `cuskss-merged --bfiles --phen --het` tests every pair at that number.
 
 `sepselect` and `orient-v-structs` (ci-gwas.py:303-358, handlers :467-476) run this package's device-backed
 mirror of cusk_postprocessing/sepselect.py (ci-gwas_amd/sepselect.py) and write the same files.
@@ -109,6 +111,9 @@ def _add_cuskss(sub, name, help_):
                        help="filestem of .bed, .bim, .fam fileset (after prep-bed): compute the correlations from the "
                             "genotypes on the GPU instead of reading --mxm/--mxp/--pxp; needs --phen")
         p.add_argument("--phen", type=str, default=None, help="path to standardized phenotype tsv (with --bfiles)")
+        p.add_argument("--het", action="store_true",
+                       help="with --bfiles: per-pair sample sizes (the individuals both variables were observed on) instead "
+                            "of the number of individuals; the result of --mxp-se/--pxp-se on the files of `sumstats --se`")
     p.set_defaults(func=cuskss, variant=name)
 
 
@@ -120,6 +125,9 @@ def _add_sumstats(sub):
     p.add_argument("outdir", type=str)
     p.add_argument("--marker-indices", metavar="marker-indices", type=str, default="NULL",
                    help="markers whose LD is written to mxm.bin (merged_blocks.ixs of merge-block-outputs); default: all")
+    p.add_argument("--se", action="store_true",
+                   help="also write mxp_se.txt and pxp_se.txt (for cuskss --mxp-se/--pxp-se): standard errors from the number "
+                        "of individuals each pair was observed on, for a .phen with NA entries")
     p.set_defaults(func=sumstats)
 
 
@@ -186,7 +194,7 @@ def cusk_argv(args) -> list[str]:
 
 
 def sumstats_argv(args) -> list[str]:
-    return [MPS_PATH, "sumstats", args.phen, args.bfiles, args.marker_indices, args.outdir]
+    return [MPS_PATH, "sumstats", args.phen, args.bfiles, args.marker_indices, args.outdir] + (["se"] if args.se else [])
 
 
 def sumstats(args):
@@ -218,13 +226,15 @@ def cuskss_bed_argv(args) -> list[str]:
             sys.exit(f"cuskss-merged: --num-samples {args.num_samples} differs from the {in_dim} individuals of "
                      f"{args.bfiles}.dim.")
     return [MPS_PATH, "cuskss-bed", args.phen, args.bfiles, args.marker_indices, args.time_index, str(args.alpha),
-            str(args.max_level_one), str(args.max_level_two), str(args.max_depth), args.outdir]
+            str(args.max_level_one), str(args.max_level_two), str(args.max_depth), args.outdir] + (["het"] if args.het else [])
 
 
 def cuskss_argv(args) -> list[str]:
     """ci-gwas.py:423-451 (validation :424-429 included)"""
     if getattr(args, "bfiles", None) is not None or getattr(args, "phen", None) is not None:
         return cuskss_bed_argv(args)
+    if getattr(args, "het", False):
+        sys.exit("cuskss-merged: --het needs --bfiles and --phen (with correlation files, give --mxp-se/--pxp-se).")
     if args.pxp == "NULL":
         sys.exit("the following arguments are required: --pxp")
     if args.num_samples is None:

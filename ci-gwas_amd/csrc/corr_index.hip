@@ -128,17 +128,55 @@ __global__ void __launch_bounds__(256) nan_to_zero_kernel(float *M, size_t count
             if (M[t] != M[t]) M[t] = 0.0f;
 }
 
+// the index list of a build over scattered markers: ascending, distinct, inside the .bed
+int check_marker_ix(cusk_engine *e, const int *marker_ix, size_t k, size_t m_total)
+{
+    if (m_total > (size_t)0x7fffffff) return fail(e, CUSK_ERR_ARG, "marker indices are 32-bit: too many markers");
+    for (size_t i = 0; i < k; i++)
+        if (marker_ix[i] < 0 || (size_t)marker_ix[i] >= m_total || (i > 0 && marker_ix[i] <= marker_ix[i - 1]))
+            return fail(e, CUSK_ERR_ARG, "marker indices must be ascending, distinct and below the number of markers (entry " +
+                                             std::to_string(i) + ")");
+    return CUSK_OK;
+}
+
+// The .bed rows marker_ix[0 .. k-1] made contiguous (bed_k): device-resident rows are gathered into e->bed_dev by the kernel
+// above (ix_d: the index list on the device; uploaded to scratch_a here when the caller has not done so), host rows are
+// packed into bed_h for the caller to upload.
+int pack_bed_rows(cusk_engine *e, const unsigned char *bed, const int *marker_ix, const int *&ix_d, size_t k, size_t m_total,
+                  size_t clb, std::vector<unsigned char> &bed_h, const unsigned char *&bed_k)
+{
+    hipStream_t s = e->stream;
+    if (is_device_pointer(bed))
+    {
+        if (!ix_d)
+        {
+            CUSK_HIP(e, e->scratch_a.ensure(sizeof(int) * k));
+            CUSK_HIP(e, hipMemcpyAsync(e->scratch_a.p, marker_ix, sizeof(int) * k, hipMemcpyHostToDevice, s));
+            ix_d = e->scratch_a.as<int>();
+        }
+        const size_t total = k * clb;
+        CUSK_HIP(e, e->bed_dev.ensure(total));
+        hipLaunchKernelGGL(gather_bed_rows_kernel, dim3((unsigned)(((total + 15) / 16 + 255) / 256)), dim3(256), 0, s, bed, ix_d,
+                           e->bed_dev.as<unsigned char>(), clb, total, m_total * clb);
+        CUSK_HIP(e, hipGetLastError());
+        bed_k = e->bed_dev.as<unsigned char>();
+    }
+    else
+    {
+        bed_h.resize(k * clb);
+        for (size_t i = 0; i < k; i++) std::memcpy(&bed_h[i * clb], bed + (size_t)marker_ix[i] * clb, clb);
+        bed_k = bed_h.data();
+    }
+    return CUSK_OK;
+}
+
 static int corr_build_indexed_impl(cusk_engine *e, const unsigned char *bed, const float *phen, const int *marker_ix, size_t k,
                                    size_t m_total, size_t N, size_t p, const float *mean, const float *std, float *C_dev,
                                    float *mxp_host)
 {
     if (!e || !bed || !phen || !marker_ix || !mean || !std || k == 0 || N == 0 || m_total == 0)
         return fail(e, CUSK_ERR_ARG, "bad arguments");
-    if (m_total > (size_t)0x7fffffff) return fail(e, CUSK_ERR_ARG, "marker indices are 32-bit: too many markers");
-    for (size_t i = 0; i < k; i++)
-        if (marker_ix[i] < 0 || (size_t)marker_ix[i] >= m_total || (i > 0 && marker_ix[i] <= marker_ix[i - 1]))
-            return fail(e, CUSK_ERR_ARG, "marker indices must be ascending, distinct and below the number of markers (entry " +
-                                             std::to_string(i) + ")");
+    if (const int rc = check_marker_ix(e, marker_ix, k, m_total)) return rc;
     CUSK_HIP(e, hipSetDevice(e->device));
     hipStream_t s = e->stream;
     const size_t clb = (N + 3) / 4;
@@ -157,20 +195,7 @@ static int corr_build_indexed_impl(cusk_engine *e, const unsigned char *bed, con
     std::vector<float> mean_h, std_h;
     const unsigned char *bed_k = nullptr;
     const float *mean_k = nullptr, *std_k = nullptr;
-    if (bed_on_dev)
-    {
-        const size_t total = k * clb;
-        CUSK_HIP(e, e->bed_dev.ensure(total));
-        hipLaunchKernelGGL(gather_bed_rows_kernel, dim3((unsigned)(((total + 15) / 16 + 255) / 256)), dim3(256), 0, s, bed, ix_d,
-                           e->bed_dev.as<unsigned char>(), clb, total, m_total * clb);
-        bed_k = e->bed_dev.as<unsigned char>();
-    }
-    else
-    {
-        bed_h.resize(k * clb);
-        for (size_t i = 0; i < k; i++) std::memcpy(&bed_h[i * clb], bed + (size_t)marker_ix[i] * clb, clb);
-        bed_k = bed_h.data();
-    }
+    if (const int rc = pack_bed_rows(e, bed, marker_ix, ix_d, k, m_total, clb, bed_h, bed_k)) return rc;
     auto gather_stat = [&](const float *src, bool on_dev, DevBuf &buf, std::vector<float> &host, const float *&out) -> hipError_t {
         if (on_dev)
         {

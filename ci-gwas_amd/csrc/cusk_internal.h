@@ -165,6 +165,7 @@ struct cusk_engine
 
     // correlation build scratch
     cusk::DevBuf bed_dev, phen_dev, mean_dev, std_dev, planes, mxp_dev, pxp_dev, mxp_bq;
+    cusk::DevBuf pc_masks, pc_counts;  // cusk_pair_counts: trait masks in the .bed bit layout, the counts before their download
     cusk::DevBuf corr_tab[2];  // batched build: block / tile tables of phase one (marker x trait) and two (marker x marker)
     void *corr_tab_pinned[2] = {nullptr, nullptr};
     size_t corr_tab_pinned_cap[2] = {0, 0};
@@ -199,6 +200,11 @@ int corr_build_impl(cusk_engine *e, const unsigned char *bed, const float *phen,
                     size_t p, const float *mean, const float *std, float *C_dev, float *mxp_host,
                     float *mxm_tri_host, float *pxp_tri_host, bool ahead = false);
 bool is_device_pointer(const void *p);  // a HIP device allocation (or a pointer into one)
+
+// corr_index.hip: index list check and row packing shared by cusk_corr_build_indexed and cusk_pair_counts
+int check_marker_ix(cusk_engine *e, const int *marker_ix, size_t k, size_t m_total);
+int pack_bed_rows(cusk_engine *e, const unsigned char *bed, const int *marker_ix, const int *&ix_d, size_t k, size_t m_total,
+                  size_t clb, std::vector<unsigned char> &bed_h, const unsigned char *&bed_k);
 
 // reference-named correlation entry points (corr_build.hip); C linkage in compat_api.hip, C++ linkage in compat_cxx.cpp
 void compat_marker_phen_corr_pearson(const unsigned char *marker_vals, const float *phen_vals, const size_t num_markers,

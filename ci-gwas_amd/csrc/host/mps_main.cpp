@@ -7,8 +7,8 @@
 //   mps cuskss <mxm> <mxp> <mxp_se> <pxp> <pxp_se> <time_index> <block_index> <blockfile>
 //              <marker_indices> <alpha> <l1> <l2> <depth> <num_samples> <outdir>   ("NULL" = absent)
 // and two commands the reference does not have, for users who hold the genotypes (see SUMSTATS_USAGE):
-//   mps sumstats   <.phen> <bfiles> <marker-indices|NULL> <outdir>
-//   mps cuskss-bed <.phen> <bfiles> <marker-indices> <time_index|NULL> <alpha> <l1> <l2> <depth> <outdir>
+//   mps sumstats   <.phen> <bfiles> <marker-indices|NULL> <outdir> [se]
+//   mps cuskss-bed <.phen> <bfiles> <marker-indices> <time_index|NULL> <alpha> <l1> <l2> <depth> <outdir> [het]
 // Differences by design: the correlation matrix never leaves HBM between the build and the
 // sweep, adjacency comes back as a bitmap, separating sets as sparse records, only the
 // retained sub-matrix is gathered to the host, and files are written with one fwrite each.
@@ -309,19 +309,24 @@ int cmd_cuskss(int argc, char **argv)
 const char *SUMSTATS_USAGE = R"(
 Compute the summary statistics cuskss reads (mxm, mxp, pxp) from genotypes and phenotypes.
 
-usage: mps sumstats <.phen> <bfiles> <marker-indices|NULL> <outdir>
+usage: mps sumstats <.phen> <bfiles> <marker-indices|NULL> <outdir> [se]
 
 arguments:
     .phen           path to standardized phenotype tsv
     bfiles          stem of .bed, .bim, .fam fileset (with the .dim, .means, .stds of mps prep)
     marker-indices  ascending global marker indices (int32 binary, merged_blocks.ixs) whose LD goes to mxm; NULL = all
     outdir          receives mxm.bin, mxp.txt (all markers), pxp.txt
+    se              also write mxp_se.txt and pxp_se.txt: standard errors from the number of individuals each pair was
+                    observed on (.phen with NA), for cuskss --mxp-se / --pxp-se
 )";
 
 const char *CUSKSS_BED_USAGE = R"(
 Run cuskss on the markers selected in all blocks, with the correlations computed from genotypes on the device.
 
-usage: mps cuskss-bed <.phen> <bfiles> <marker-indices> <time_index|NULL> <alpha> <max_level_one> <max_level_two> <depth> <outdir>
+usage: mps cuskss-bed <.phen> <bfiles> <marker-indices> <time_index|NULL> <alpha> <max_level_one> <max_level_two> <depth> <outdir> [het]
+
+    het             test every marker-trait and trait-trait pair at the number of individuals it was observed on (.phen
+                    with NA) instead of all of them: the result of cuskss on the files of `mps sumstats ... se`
 )";
 
 // .phen, the prep files and the marker selection; the arrays every kernel reads are copied to the device once
@@ -418,9 +423,9 @@ struct GenoInputs
     }
 
     // n x n matrix (selected markers, then traits) built where the sweep reads it
-    void build_square(cusk_engine *e, float *C_dev)
+    void build_square(cusk_engine *e, float *C_dev, float *mxp_host = nullptr)
     {
-        if (cusk_corr_build_indexed(e, bed_rows(), phen_d, ixs.data(), k(), m(), N(), p(), means_d, stds_d, C_dev, nullptr) !=
+        if (cusk_corr_build_indexed(e, bed_rows(), phen_d, ixs.data(), k(), m(), N(), p(), means_d, stds_d, C_dev, mxp_host) !=
             CUSK_OK)
             engine_die("correlation build", e);
     }
@@ -442,6 +447,8 @@ int cmd_sumstats(int argc, char **argv)
         std::exit(1);
     }
     const std::string phen_path = argv[2], bfiles = argv[3], index_path = argv[4], outdir = argv[5];
+    const bool with_se = argc > 6;
+    if (with_se && std::string(argv[6]) != "se") die(std::string("sumstats: unknown trailing argument ") + argv[6]);
     PhaseTimer tm;
     check_path(outdir);
     GenoInputs in;
@@ -482,6 +489,21 @@ int cmd_sumstats(int argc, char **argv)
             engine_die("marker-trait correlations", e);
     }
     tm.mark("genome-wide mxp");
+    std::vector<int> mxp_n, pxp_n;
+    if (with_se)
+    {
+        std::cout << "Counting complete observations per pair" << std::endl;
+        mxp_n.resize(m * p);
+        pxp_n.resize(p * p);
+        for (size_t c0 = 0; c0 < m; c0 += chunk)
+        {
+            const size_t mc = std::min(chunk, m - c0);
+            if (cusk_pair_counts(e, in.bed_rows() + c0 * clb, in.phen_d, nullptr, mc, mc, in.N(), p, &mxp_n[c0 * p],
+                                 c0 == 0 ? pxp_n.data() : nullptr) != CUSK_OK)
+                engine_die("pair counts", e);
+        }
+        tm.mark("genome-wide pair counts");
+    }
 
     std::cout << "Writing mxm.bin, mxp.txt, pxp.txt" << std::endl;
     auto cstrs = [](const std::vector<std::string> &v) {
@@ -494,6 +516,13 @@ int cmd_sumstats(int argc, char **argv)
     if (cusk_sumstats_write(outdir.c_str(), tri.data(), k, mxp.data(), m, p, pxp.data(), chr.data(), snp.data(), ref.data(),
                             names.data(), err, sizeof(err)) != CUSK_OK)
         die(err);
+    if (with_se)
+    {
+        std::cout << "Writing mxp_se.txt, pxp_se.txt" << std::endl;
+        if (cusk_sumstats_write_se(outdir.c_str(), mxp.data(), mxp_n.data(), m, p, pxp.data(), pxp_n.data(), chr.data(), snp.data(),
+                                   ref.data(), names.data(), err, sizeof(err)) != CUSK_OK)
+            die(err);
+    }
     tm.mark("write files");
     cusk_engine_destroy(e);
     std::cout << "Done." << std::endl;
@@ -511,6 +540,8 @@ int cmd_cuskss_bed(int argc, char **argv)
     const float alpha = std::stof(argv[6]);
     const int max_level_one = std::stoi(argv[7]), max_level_two = std::stoi(argv[8]), depth = std::stoi(argv[9]);
     const std::string outdir = argv[10];
+    const bool het = argc > 11;
+    if (het && std::string(argv[11]) != "het") die(std::string("cuskss-bed: unknown trailing argument ") + argv[11]);
     if (index_path == "NULL") die("cuskss-bed needs marker indices");
     check_path(outdir);
     const bool time_indexed = time_index_path != "NULL";
@@ -539,16 +570,46 @@ int cmd_cuskss_bed(int argc, char **argv)
     std::iota(gc.new_to_old.begin(), gc.new_to_old.end(), 0);
     {
         DevMat C(n * n);
-        in.build_square(e, C.p);
+        std::vector<float> mxp;
+        if (het) mxp.resize(k * p);
+        in.build_square(e, C.p, het ? mxp.data() : nullptr);
+        if (het)
+        {
+            // The sample sizes `cuskss` would load from the files of `mps sumstats ... se` (load_mxp, load_pxp and
+            // make_square_cuskss_inputs, cli.cpp:89-173): N between markers; the count of complete observations, through
+            // the standard error the file would hold, between a marker or trait and a trait; NaN where the correlation
+            // is NaN and on the trait diagonal (pxp_se holds nan there).  pxp is read as the loader reads it: the
+            // upper triangle, mirrored.
+            std::cout << "Counting complete observations per pair" << std::endl;
+            std::vector<int> traits(p);
+            std::iota(traits.begin(), traits.end(), (int)k);
+            const std::vector<float> pxp = gather(e, C.p, (int)n, traits);
+            std::vector<int> mxp_n(k * p), pxp_n(p * p);
+            if (cusk_pair_counts(e, in.bed_rows(), in.phen_d, in.ixs.data(), k, in.m(), in.N(), p, mxp_n.data(), pxp_n.data()) !=
+                CUSK_OK)
+                engine_die("pair counts", e);
+            const float nan = std::numeric_limits<float>::quiet_NaN();
+            auto ess_of = [&](float r, int count) { return std::isnan(r) ? nan : cusk_ess_from_se(r, cusk_se_from_count(r, count)); };
+            gc.ess.assign(n * n, num_samples);
+            for (size_t i = 0; i < k; i++)
+                for (size_t t = 0; t < p; t++)
+                    gc.ess[i * n + k + t] = gc.ess[(k + t) * n + i] = ess_of(mxp[i * p + t], mxp_n[i * p + t]);
+            for (size_t a = 0; a < p; a++)
+            {
+                gc.ess[(k + a) * n + k + a] = nan;
+                for (size_t b = a + 1; b < p; b++)
+                    gc.ess[(k + a) * n + k + b] = gc.ess[(k + b) * n + k + a] = ess_of(pxp[a * p + b], pxp_n[a * p + b]);
+            }
+        }
         // what the loaders of the three files do to a NaN correlation (host_io.h: load_mxm_into, load_mxp, load_pxp)
         if (cusk_nan_to_zero(e, C.p, n * n) != CUSK_OK) engine_die("NaN -> 0", e);
         std::cout << "Starting first cusk stage" << std::endl;
-        gc = run_cusk(e, gc, th, num_samples, false, depth, max_level_one, time_index_traits, C.p);
+        gc = run_cusk(e, gc, th, num_samples, het, depth, max_level_one, time_index_traits, C.p);
     }
     if (max_level_two > 0)
     {
         std::cout << "Starting second cusk stage" << std::endl;
-        gc = run_cusk(e, gc, th, num_samples, false, depth, max_level_two, time_index_traits);
+        gc = run_cusk(e, gc, th, num_samples, het, depth, max_level_two, time_index_traits);
     }
     std::cout << "Retained " << gc.num_markers() << " markers" << std::endl;
     write_gc(gc, make_path(outdir, "cuskss_merged", ""));
@@ -562,7 +623,7 @@ usage: mps <command> [<args>]
 commands:
     cusk                    Run the skeleton search on a single block of block diagonal genomic covariance matrix
     cuskss                  Run the skeleton search on a block of markers and traits with pre-computed correlations.
-    sumstats                Compute the correlation files cuskss reads (mxm, mxp, pxp) from genotypes and phenotypes
+    sumstats                Compute the correlation files cuskss reads (mxm, mxp, pxp; with `se` also mxp_se, pxp_se) from genotypes and phenotypes
     cuskss-bed              cuskss on the merged marker selection with the correlations computed from genotypes
     block                   Tile the marker x marker correlation matrix of every chromosome into LD blocks
     prep                    Prepare input (PLINK) .bed file for cusk: .dim, .means, .stds, .modes

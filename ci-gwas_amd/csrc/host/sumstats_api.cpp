@@ -3,10 +3,16 @@
 // /root/reference/cusk/src/marker_summary_stats.cpp:8-24, marker_trait_summary_stats.cpp:40-299,
 // trait_summary_stats.cpp:5-169).  Floats go out with nine significant digits, which a parser that rounds to float32
 // reads back exactly.  Every write and close is checked: a full disk must not leave a truncated mxp behind a zero status.
+//
+// cusk_sumstats_write_se adds the two standard-error files from per-pair observation counts (cusk_pair_counts).  The
+// loaders turn a standard error back into a sample size with ess = ((1 - r^2) / se)^2 (host::ess_from_se), and the sweep
+// truncates every sample size to int before it averages them (mean_ess of the reference), so cusk_se_from_count picks the
+// float se from which that chain gives back the count itself, not count - 1.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -124,7 +130,61 @@ void write_pxp(const std::string &path, const float *pxp, size_t p, const char *
     out.close();
 }
 
+// (int)ess == count without converting an out-of-range float
+inline bool recovers(float r, float se, int count)
+{
+    const double e = (double)host::ess_from_se(r, se);
+    return e >= (double)count && e < (double)count + 1.0;
+}
+
 }  // namespace
+
+extern "C" float cusk_ess_from_se(float r, float se) { return host::ess_from_se(r, se); }
+
+// se = (1 - r^2) / sqrt(count) in the loaders' float/double mix, moved by one ulp towards the side that makes
+// (int)cusk_ess_from_se(r, se) == count when the plain value gives count - 1 or count + 1 (it does for about three pairs
+// in ten).  One ulp is enough for every count up to two million; beyond that the spacing of float32 near `count` exceeds
+// what one ulp of se can correct for some pairs, and where neither neighbour works the plain value is returned.
+extern "C" float cusk_se_from_count(float r, int count)
+{
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    if (std::isnan(r) || count <= 0 || !(r * r < 1.0f)) return nan;
+    const float se = (float)((1.0 - (double)(r * r)) / std::sqrt((double)count));
+    if (recovers(r, se, count)) return se;
+    const float inf = std::numeric_limits<float>::infinity();
+    for (const float cand : {std::nextafterf(se, 0.0f), std::nextafterf(se, inf)})
+        if (cand > 0.0f && recovers(r, cand, count)) return cand;
+    return se;
+}
+
+extern "C" int cusk_sumstats_write_se(const char *outdir, const float *mxp, const int *mxp_n, size_t m_total, size_t p,
+                                      const float *pxp_square, const int *pxp_n, const char *const *chr, const char *const *snp,
+                                      const char *const *ref, const char *const *trait_names, char *err, size_t err_len)
+{
+    auto report = [&](const std::string &msg, int code) {
+        if (err && err_len) std::snprintf(err, err_len, "%s", msg.c_str());
+        return code;
+    };
+    if (!outdir || !mxp || !mxp_n || !pxp_square || !pxp_n || !chr || !snp || !ref || !trait_names || m_total == 0 || p == 0)
+        return report("cusk_sumstats_write_se: bad arguments", CUSK_ERR_ARG);
+    try
+    {
+        const float nan = std::numeric_limits<float>::quiet_NaN();
+        std::vector<float> se(m_total * p);
+        for (size_t i = 0; i < m_total * p; i++) se[i] = std::isnan(mxp[i]) ? nan : cusk_se_from_count(mxp[i], mxp_n[i]);
+        write_mxp(host::make_path(outdir, "mxp_se", ".txt"), se.data(), m_total, p, chr, snp, ref, trait_names);
+        se.assign(p * p, nan);  // the diagonal stays NaN: see cusk_hip.h
+        for (size_t a = 0; a < p; a++)
+            for (size_t b = 0; b < p; b++)
+                if (a != b && !std::isnan(pxp_square[a * p + b])) se[a * p + b] = cusk_se_from_count(pxp_square[a * p + b], pxp_n[a * p + b]);
+        write_pxp(host::make_path(outdir, "pxp_se", ".txt"), se.data(), p, trait_names);
+    }
+    catch (const std::exception &ex)
+    {
+        return report(ex.what(), CUSK_ERR_ARG);
+    }
+    return CUSK_OK;
+}
 
 extern "C" int cusk_sumstats_write(const char *outdir, const float *mxm_tri, size_t k, const float *mxp, size_t m_total, size_t p,
                                    const float *pxp_square, const char *const *chr, const char *const *snp, const char *const *ref,

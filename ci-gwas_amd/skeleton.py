@@ -103,6 +103,41 @@ def sumstats_write(outdir: str, mxm_tri, mxp, pxp, chr_ids, snp_ids, ref_alleles
         raise RuntimeError(f"cusk_sumstats_write failed ({rc}): {err.value.decode()}")
 
 
+def ess_from_se(r: float, se: float) -> float:
+    """cusk_ess_from_se: the sample size the mxp / pxp loaders make of a correlation and its standard error"""
+    return float(lib().cusk_ess_from_se(float(np.float32(r)), float(np.float32(se))))
+
+
+def se_from_count(r: float, count: int) -> float:
+    """cusk_se_from_count: the standard error written for a Pearson correlation on `count` complete observations, chosen
+    so that int(ess_from_se(r, se)) == count"""
+    return float(lib().cusk_se_from_count(float(np.float32(r)), int(count)))
+
+
+def sumstats_write_se(outdir: str, mxp, mxp_n, pxp, pxp_n, chr_ids, snp_ids, ref_alleles, trait_names) -> None:
+    """cusk_sumstats_write_se (host only): <outdir>/mxp_se.txt, pxp_se.txt from the correlations sumstats_write wrote and
+    the per-pair observation counts of Engine.pair_counts (mxp_n m_total x p, pxp_n p x p)"""
+    pxp = np.ascontiguousarray(pxp, np.float32)
+    p = pxp.shape[0]
+    mxp = np.ascontiguousarray(mxp, np.float32).reshape(-1, p)
+    m_total = mxp.shape[0]
+    mxp_n = np.ascontiguousarray(mxp_n, np.int32).reshape(-1, p)
+    pxp_n = np.ascontiguousarray(pxp_n, np.int32)
+    if pxp.shape != (p, p) or pxp_n.shape != (p, p) or mxp_n.shape != mxp.shape:
+        raise ValueError("pxp and pxp_n must be p x p, mxp and mxp_n m_total x p")
+    if not (len(chr_ids) == len(snp_ids) == len(ref_alleles) == m_total) or len(trait_names) != p:
+        raise ValueError("one chr / snp / ref entry per mxp row and one name per trait are needed")
+
+    def strings(v):
+        return (C.c_char_p * len(v))(*[str(x).encode() for x in v])
+
+    err = C.create_string_buffer(512)
+    rc = lib().cusk_sumstats_write_se(str(outdir).encode(), _ptr(mxp), _ptr(mxp_n), m_total, p, _ptr(pxp), _ptr(pxp_n),
+                                      strings(chr_ids), strings(snp_ids), strings(ref_alleles), strings(trait_names), err, len(err))
+    if rc != 0:
+        raise RuntimeError(f"cusk_sumstats_write_se failed ({rc}): {err.value.decode()}")
+
+
 @dataclass
 class Stats:
     level: int
@@ -330,6 +365,28 @@ class Engine:
         self._check(lib().cusk_corr_build_indexed(self.h, bed_p, _ptr(phen), _ptr(ix), len(ix), int(m_total), int(N), int(p),
                                                   means_p, stds_p, C_dev, _ptr(mxp)))
         return mxp
+
+    def pair_counts(self, bed, phen, N: int, p: int, k: int | None = None, marker_ix=None, m_total: int | None = None):
+        """cusk_pair_counts -> (mxp_n k x p, pxp_n p x p) int32: per pair the individuals with both values observed (marker
+        not missing, trait not NaN).  bed / phen: host arrays or DeviceArray copies; the markers are rows `marker_ix`
+        (ascending) of the m_total rows of bed, or its first k rows (default: all rows of a host array)"""
+        clb = (int(N) + 3) // 4
+        if isinstance(bed, DeviceArray):
+            bed_p, rows = bed.ptr, bed.nbytes // clb
+        else:
+            bed = np.ascontiguousarray(bed, np.uint8)
+            bed_p, rows = _ptr(bed), bed.size // clb
+        if isinstance(phen, DeviceArray):
+            phen_p = phen.ptr
+        else:
+            phen = np.ascontiguousarray(phen, np.float32)
+            phen_p = _ptr(phen)
+        m_total = int(rows if m_total is None else m_total)
+        ix = np.ascontiguousarray(marker_ix, np.int32) if marker_ix is not None else None
+        k = int(len(ix) if ix is not None else (m_total if k is None else k))
+        mxp_n, pxp_n = np.zeros((k, int(p)), np.int32), np.zeros((int(p), int(p)), np.int32)
+        self._check(lib().cusk_pair_counts(self.h, bed_p, phen_p, _ptr(ix), k, m_total, int(N), int(p), _ptr(mxp_n), _ptr(pxp_n)))
+        return mxp_n, pxp_n
 
     def pack_lower_tri(self, C_dev: int, n: int, k: int) -> np.ndarray:
         """the leading k x k block of the n x n device matrix as the `mxm` file holds it: lower triangle with diagonal,

@@ -290,6 +290,36 @@ int cusk_nan_to_zero(cusk_engine *e, float *M_dev, size_t count);
 int cusk_sumstats_write(const char *outdir, const float *mxm_tri, size_t k, const float *mxp, size_t m_total, size_t p,
                         const float *pxp_square, const char *const *chr, const char *const *snp, const char *const *ref,
                         const char *const *trait_names, char *err, size_t err_len);
+/* Complete-observation counts of the Pearson blocks of cusk_corr_build / cusk_corr_build_indexed, for phenotype tables
+ * with gaps (NaN): the correlation kernels divide by these numbers and drop them, a skeleton run with per-pair sample
+ * sizes (cusk_run_hetcor with N_dev) needs them.
+ *   mxp_n_host[i * p + t]  individuals for which marker i is not missing (.bed code != 01) and trait t is not NaN
+ *   pxp_n_host[a * p + b]  individuals for which neither trait a nor trait b is NaN (symmetric; diagonal: the trait's own)
+ * The markers are rows marker_ix[0 .. k-1] of a .bed of m_total rows (HOST array; ascending, distinct), or rows 0 .. k-1 when
+ * marker_ix is NULL.  bed and phen (p x N, trait-major) may each be host memory or device-resident; scattered resident
+ * rows go through the row-gather scratch of cusk_corr_build_indexed.  Counts are exact 32-bit integers; individuals are
+ * 0 .. N-1 whatever the last byte of a row or the memory behind it holds.  Either output may be NULL.  Returns when the
+ * counts are there. */
+int cusk_pair_counts(cusk_engine *e, const unsigned char *bed, const float *phen, const int *marker_ix, size_t k,
+                     size_t m_total, size_t N, size_t p, int *mxp_n_host, int *pxp_n_host);
+/* Host only.  The sample size the mxp / pxp loaders of `cuskss` make of a correlation and its standard error:
+ * ((1 - r^2) / se)^2 with their float / double mix (marker_trait_summary_stats.cpp:161-164). */
+float cusk_ess_from_se(float r, float se);
+/* Host only.  The standard error to write for a Pearson correlation r estimated on `count` observations:
+ * (float)((1 - r^2) / sqrt(count)), moved by at most one ulp so that (int)cusk_ess_from_se(r, se) == count -- the sweep
+ * truncates sample sizes to int (mean_ess), and the plain value gives count - 1 for about three pairs in ten.  That
+ * holds for every count up to 2,000,000; at 8 million about 9 % of pairs and at 16 million about a third have no such
+ * neighbour and get the plain value.  NaN when r is NaN, count <= 0 or r^2 >= 1. */
+float cusk_se_from_count(float r, int count);
+/* Host only.  <outdir>/mxp_se.txt and <outdir>/pxp_se.txt beside the files of cusk_sumstats_write, in the formats of
+ * mxp.txt / pxp.txt (same header and label columns, %.9g): se = cusk_se_from_count(correlation, count) with the counts of
+ * cusk_pair_counts (mxp_n m_total x p, pxp_n p x p), NaN where the correlation is NaN (the loaders do not read it there);
+ * a NaN goes out as NA in mxp_se and nan in pxp_se.  The diagonal of pxp_se is nan: the pxp loader reads it, and any se
+ * beside r = 1 is a sample size of 0 or NaN; NaN it is, on this route and in `mps cuskss-bed ... het` alike (a literal 0
+ * would mean 0 / 0 to the loader, which not every reader of these files survives).  Errors as cusk_sumstats_write. */
+int cusk_sumstats_write_se(const char *outdir, const float *mxp, const int *mxp_n, size_t m_total, size_t p,
+                           const float *pxp_square, const int *pxp_n, const char *const *chr, const char *const *snp,
+                           const char *const *ref, const char *const *trait_names, char *err, size_t err_len);
 /* timing of the last cusk_corr_build: [0] decode, [1] count GEMM, [2] mxp/pxp, [3] total (ms) */
 void cusk_corr_timing(const cusk_engine *e, float *ms4);
 

@@ -9,7 +9,11 @@ loop-carried), the kernel computes on stale data without any diagnostic.  This s
 to device assembly and walks every kernel that contains such loads: from each `global_load_dwordx4 v[a:b]` until the
 `s_waitcnt vmcnt(N)` that retires it (loads retire in order: after vmcnt(N) only the N youngest are pending), no
 instruction may read or write v[a:b].  Loop back-edges are followed once with the state at the branch.  Exit status 1
-on a violation.  usage: check_asm_prefetch.py <file.hip> [hipcc flags...]   (or  --asm file.s)
+on a violation.  usage: check_asm_prefetch.py [--kernels PAT,PAT] <file.hip> [hipcc flags...]   (or  --asm file.s)
+
+--kernels names other kernels to walk (substrings of their mangled names) instead of mxm_fp4_kernel<true>: the Makefile
+runs the same walk over the count kernels of csrc/pair_counts.hip, whose waits are the compiler's own, so that a later
+hand-issued prefetch there is held to the same rule from its first build.
 """
 import re
 import subprocess
@@ -96,6 +100,10 @@ def check_function(name, lines):
 
 
 def main():
+    pats = [KERNEL_PAT]
+    if sys.argv[1] == "--kernels":
+        pats = sys.argv[2].split(",")
+        del sys.argv[1:3]
     if sys.argv[1] == "--asm":
         text = open(sys.argv[2]).read()
     else:
@@ -106,7 +114,7 @@ def main():
     funcs = re.findall(r"^(_Z\w+):\s*;[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, flags=re.S | re.M)
     checked, all_err = 0, []
     for name, body in funcs:
-        if KERNEL_PAT not in name:
+        if not any(pat in name for pat in pats):
             continue
         lines = [l.strip() for l in body.splitlines()]
         errs, nl = check_function(name, lines)

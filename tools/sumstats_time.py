@@ -2,6 +2,7 @@
 """Wall-clock phases of `mps sumstats` and the cost of the indexed correlation build beside the contiguous one.
 
     python tools/sumstats_time.py [--markers 40000] [--samples 16384] [--traits 20] [--selected 5000] [--repeats 5]
+                                  [--se] [--no-mps]
 
 Writes a synthetic PLINK set (binomial dosages, 0.1 % missing) + .phen + prep files to a temporary directory, then
   1. runs `mps sumstats` with CUSK_TIMING=1 once to warm up and `--repeats` times more, and prints the median of every
@@ -9,7 +10,12 @@ Writes a synthetic PLINK set (binomial dosages, 0.1 % missing) + .phen + prep fi
   2. in this process, with the .bed resident in HBM: `cusk_corr_build_indexed` on the selected markers against
      `cusk_corr_build` on the same rows made contiguous on the host and uploaded beforehand -- warm-up, `--repeats`
      calls each, median of the call's wall clock and of the SNP x SNP kernel's HIP-event time -- and
-     `cusk_pack_lower_tri` to the host.
+     `cusk_pack_lower_tri` to the host;
+  3. the count pass (`cusk_pair_counts`: trait masks, marker x trait and trait x trait counts, download) on the selected
+     rows, resident and contiguous, beside the marker x trait build of the same rows (`cusk_corr_build` without a
+     matrix), both as the call's wall clock; and the count pass's share of the HBM peak, counting the .bed rows and the
+     trait masks once each.
+`--se` runs `mps sumstats ... se` in step 1 (one more phase mark: the genome-wide pair counts), `--no-mps` skips step 1.
 The difference between the two build calls is the row gather (k * ceil(N/4) bytes read and written) plus the upload of
 the index list.
 """
@@ -53,6 +59,9 @@ def main():
     ap.add_argument("--traits", type=int, default=20)
     ap.add_argument("--selected", type=int, default=5000)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--se", action="store_true", help="step 1 with the standard-error files")
+    ap.add_argument("--no-mps", action="store_true", help="skip step 1")
+    ap.add_argument("--hbm-peak", type=float, default=8.0e12, help="bytes per second the bandwidth share refers to")
     a = ap.parse_args()
     import cigwas_amd as cg
     from cigwas_amd import cli
@@ -69,8 +78,9 @@ def main():
         out = os.path.join(d, "out")
         os.mkdir(out)
         marks = {}
-        for rep in range(a.repeats + 1):
-            r = subprocess.run([cli.MPS_PATH, "sumstats", phen_path, stem, os.path.join(d, "sel.ixs"), out], check=True,
+        for rep in range(0 if a.no_mps else a.repeats + 1):
+            r = subprocess.run([cli.MPS_PATH, "sumstats", phen_path, stem, os.path.join(d, "sel.ixs"), out] + (["se"] if a.se else []),
+                               check=True,
                                capture_output=True, text=True, env=dict(os.environ, CUSK_TIMING="1"))
             if rep == 0:
                 continue  # warm-up: page cache, code objects
@@ -82,11 +92,12 @@ def main():
                 if mt:
                     marks.setdefault("device: marker x marker kernel", []).append(float(mt.group(1)))
                     marks.setdefault("device: marker x trait + trait x trait kernels", []).append(float(mt.group(2)))
-        print(f"mps sumstats, median of {a.repeats} runs after one warm-up (ms):")
-        for name, v in marks.items():
-            print(f"  {name}: {statistics.median(v):.2f}  (min {min(v):.2f}, max {max(v):.2f})")
-        sizes = {f: os.path.getsize(os.path.join(out, f)) for f in ("mxm.bin", "mxp.txt", "pxp.txt")}
-        print(f"  files: {sizes}")
+        if not a.no_mps:
+            print(f"mps sumstats{' se' if a.se else ''}, median of {a.repeats} runs after one warm-up (ms):")
+            for name, v in marks.items():
+                print(f"  {name}: {statistics.median(v):.2f}  (min {min(v):.2f}, max {max(v):.2f})")
+            sizes = {f: os.path.getsize(os.path.join(out, f)) for f in sorted(os.listdir(out))}
+            print(f"  files: {sizes}")
 
         eng = cg.Engine(0)
         n = k + p
@@ -121,6 +132,30 @@ def main():
             eng.pack_lower_tri(Cd.ptr, n, k)
             t_pack.append((time.perf_counter() - t) * 1e3)
         print(f"pack_lower_tri to the host ({2 * k * (k + 1) / 1e6:.1f} MB): {statistics.median(t_pack):.3f} ms")
+
+        phen_d = cg.DeviceArray(phen)
+        mxp_host = np.zeros(k * p, np.float32)
+
+        def counts():
+            eng.pair_counts(sel_d, phen_d, N, p, k=k)
+
+        def mxp_only():
+            eng._check(lib().cusk_corr_build(eng.h, sel_d.ptr, phen_d.ptr, k, N, p, smean_d.ptr, sstd_d.ptr, None, mxp_host.ctypes.data))
+
+        pc = {}
+        for name, fn in (("pair counts", counts), ("marker x trait build", mxp_only)):
+            fn()
+            wall = []
+            for _ in range(max(a.repeats, 20)):
+                t = time.perf_counter()
+                fn()
+                wall.append((time.perf_counter() - t) * 1e3)
+            pc[name] = (statistics.median(wall), min(wall))
+            print(f"{name} of {k} resident rows: call {pc[name][0]:.3f} ms (min {pc[name][1]:.3f})")
+        moved = k * ((N + 3) // 4) + p * ((N + 63) // 64) * 16
+        print(f"pair counts: {moved / 1e6:.1f} MB (.bed rows + trait masks, once each) in {pc['pair counts'][0]:.3f} ms = "
+              f"{moved / (pc['pair counts'][0] * 1e-3) / 1e9:.1f} GB/s, {100 * moved / (pc['pair counts'][0] * 1e-3) / a.hbm_peak:.1f} % of "
+              f"{a.hbm_peak / 1e12:.1f} TB/s; {pc['pair counts'][0] / pc['marker x trait build'][0]:.2f} x the marker x trait build")
         eng.close()
 
 
