@@ -13,7 +13,8 @@ with missing values `sumstats --se` adds the two standard-error files (from the 
 observed on) and `cuskss-merged --bfiles --phen --het` tests every pair at that number.
 
 `sepselect` and `orient-v-structs` (ci-gwas.py:303-358, handlers :467-476) run this package's device-backed
-mirror of cusk_postprocessing/sepselect.py (ci-gwas_amd/sepselect.py) and write the same files.
+mirror of cusk_postprocessing/sepselect.py (ci-gwas_amd/sepselect.py) and write the same files.  With `--het` they
+decide at the per-pair sample sizes a heterogeneous `cuskss-merged` run left in `cuskss_merged_ssz.mtx`.
 `merge-block-outputs` (ci-gwas.py:255-271, :459-464) and the post-step of a merged `cuskss` run (:452-456) use this
 package's mirror of the reference's merge module (ci-gwas_amd/merge.py), pinned by files the reference's own code
 wrote (tests/golden/merge).  The rest of the downstream (srfci, mvivw) is the reference's own code and consumes the
@@ -155,6 +156,9 @@ def _add_sepselect(sub):
             p.add_argument("--orientation-prior", metavar="orientation-prior", type=str, default=None,
                            help="matrix of (0, 1) (32 bit integers, binary) of dims (n_trait, n_trait) indicating "
                                 "directions to be forced. ")
+        p.add_argument("--het", action="store_true",
+                       help="decide at the per-pair sample sizes of <cusk-result-stem>_ssz.mtx (written by cuskss-merged "
+                            "--het) instead of num-samples, which is then not used")
         p.set_defaults(func=func)
 
 
@@ -281,7 +285,7 @@ def run_sepselect(args):
     """ci-gwas.py:467-470"""
     from .sepselect import sepselect_merged
 
-    merged_cusk = sepselect_merged(args.cusk_result_stem, args.alpha, args.num_samples)
+    merged_cusk = sepselect_merged(args.cusk_result_stem, args.alpha, args.num_samples, het=args.het)
     merged_cusk.to_file(f"{os.path.dirname(args.cusk_result_stem)}/max_sep_min_pc")
     print("Sepselect done.")
 
@@ -290,7 +294,8 @@ def run_v_struct(args):
     """ci-gwas.py:473-476"""
     from .sepselect import orient_v_structures_merged
 
-    merged_cusk = orient_v_structures_merged(args.cusk_result_stem, args.alpha, args.num_samples, args.orientation_prior)
+    merged_cusk = orient_v_structures_merged(args.cusk_result_stem, args.alpha, args.num_samples, args.orientation_prior,
+                                             het=args.het)
     merged_cusk.to_file(f"{os.path.dirname(args.cusk_result_stem)}/max_sep_min_pc")
     print("Sepselect / v-structs done.")
 

@@ -240,7 +240,7 @@ inline void write_binary(const std::string &path, const T *data, size_t count)
         p += w;
         left -= (size_t)w;
     }
-    ::close(fd);
+    if (::close(fd) != 0) die("cannot write " + path);
 }
 
 // .phen: header skipped, FID IID dropped, "NA" -> NaN, returned column-major (phen.cpp:9-74)

@@ -180,6 +180,9 @@ void write_gc(const GC &gc, const std::string &base)
     r.G = gc.G;
     r.C = gc.C;
     write_reduced(r, base, false);
+    // heterogeneous runs: the sample sizes of the retained variables beside .corr, same order (float32, num_var^2), for
+    // sepselect --het
+    if (!gc.ess.empty()) write_binary(base + ".ess", gc.ess.data(), gc.ess.size());
 }
 
 int cmd_cuskss(int argc, char **argv)

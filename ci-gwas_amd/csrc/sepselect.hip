@@ -14,10 +14,18 @@
 // precision.  Mathematically the same partial correlations as the inverse gives; rounding differs in the last
 // bits, which can only matter for exact ties (documented in DESIGN.md; the parity tests compare every output
 // file with the reference's).
+//
+// Heterogeneous mode (HET, cusk_sepselect_greedy_het): every decision is taken at the sample size of the variables it
+// is about instead of one num_samples.  The threshold of a decision over V = {i, j} + S + {t}, |S + {t}| = l, is
+// q / sqrt(mean - l - 3) with mean = (sum of the sizes of all (l + 2)(l + 1) / 2 unordered pairs of V) / that count:
+// the hetcor sweep's mean_ess in this kernel's double arithmetic.  The wave keeps the running sum over {i, j} + S and
+// adds the picked candidate's l + 1 sizes once per round, read from global memory.  Which candidate a round picks does
+// not depend on the threshold; with every size equal to N the mean is exactly N and the mode reproduces the table.
 #include "cusk_internal.h"
 
 #include <algorithm>
 #include <cmath>
+#include <string>
 #include <vector>
 
 namespace cusk {
@@ -42,6 +50,10 @@ struct SepBatch
     const int *list;        // pair ids of this launch
     double *ws;             // global work space for pairs beyond the LDS classes
     long long ws_stride;    // doubles per pair in ws
+    // HET mode only (thr is not read then)
+    const int *tn;          // n x p: sample size of variable v with trait t (layout of tc)
+    const int *pair_n;      // sample size of (pair_i[k], pair_j[k])
+    double q;               // norm.ppf(1 - alpha / 2)
 };
 
 // e = a * w + c with 0 <= c < w: float reciprocal while it is exact (w <= 512, e < 2^18), integer division beyond
@@ -53,7 +65,15 @@ __device__ __forceinline__ void split_index(int e, int w, float inv_w, int &a, i
 
 __device__ __forceinline__ double abs_fisher_z(double r) { return fabs(0.5 * log(fabs((1.0 + r) / (1.0 - r)))); }
 
-template <bool IN_LDS>
+// q / sqrt(mean - l - 3), mean = nsum / number of unordered pairs of l + 2 variables; a negative or NaN radicand gives
+// NaN, and the comparison against it is false ("not independent")
+__device__ __forceinline__ double het_thr(double q, long long nsum, int l)
+{
+    const double mean = (double)nsum / (double)((l + 2) * (l + 1) / 2);
+    return q / sqrt(mean - (double)l - 3.0);
+}
+
+template <bool IN_LDS, bool HET>
 __global__ void __launch_bounds__(64) sepselect_kernel(SepBatch b, int cap)
 {
     extern __shared__ double s_mem[];
@@ -91,7 +111,9 @@ __global__ void __launch_bounds__(64) sepselect_kernel(SepBatch b, int cap)
     double rii = 1.0, rjj = 1.0, rij = b.pair_c[pid];
     int status = 0;
     if (rii * rjj - rij * rij == 0.0) status = 2;  // the 2 x 2 matrix itself is singular
-    bool separated = abs_fisher_z(rij / sqrt(fabs(rii * rjj))) < b.thr[0];
+    [[maybe_unused]] long long nsum = 0;  // HET: sizes summed over the unordered pairs of {i, j} + S
+    if constexpr (HET) nsum = b.pair_n[pid];
+    bool separated = abs_fisher_z(rij / sqrt(fabs(rii * rjj))) < (HET ? het_thr(b.q, nsum, 0) : b.thr[0]);
     bool seen_minimum = false;
     double previous = INFINITY;
     int len = 0;
@@ -136,8 +158,17 @@ __global__ void __launch_bounds__(64) sepselect_kernel(SepBatch b, int cap)
             break;
         }
         if (best > previous && separated && !seen_minimum) seen_minimum = true;
-        const bool indep = best < b.thr[size];
+        [[maybe_unused]] long long nadd = 0;  // HET: sizes of the pick with i, j and every member of S
+        if constexpr (HET)
+        {  // S is read back from sel: lane 0 stored it before the barriers of the previous round's list update
+            const int tp = b.cand[c0 + rem[pick]];
+            for (int k = lane; k < len; k += 64) nadd += b.tn[(size_t)b.sel[c0 + k] * p + tp];
+            if (lane == 0) nadd += (long long)b.tn[(size_t)vi * p + tp] + (long long)b.tn[(size_t)vj * p + tp];
+            for (int o = 32; o > 0; o >>= 1) nadd += __shfl_xor(nadd, o);
+        }
+        const bool indep = best < (HET ? het_thr(b.q, nsum + nadd, size) : b.thr[size]);
         if (separated && !indep) break;
+        if constexpr (HET) nsum += nadd;
         separated = separated || indep;
         previous = best;
         const int kp = rem[pick];
@@ -191,36 +222,46 @@ size_t sep_bytes(int cap) { return sizeof(double) * ((size_t)cap * (cap | 1) + 4
 
 int sepselect_greedy_impl(cusk_engine *e, const double *trait_corr, long long n, int p, long long npairs, const int *pair_i,
                           const int *pair_j, const double *pair_corr, const long long *cand_off, const int *cand,
-                          const double *thr, int nthr, int *sel, int *sel_len, int *flags, float *kernel_ms)
+                          const double *thr, int nthr, bool het, const int *trait_n, const int *pair_n, double q, int *sel,
+                          int *sel_len, int *flags, float *kernel_ms)
 {
-    if (!e || !trait_corr || n <= 0 || p <= 0 || npairs < 0 || !cand_off || !thr || !sel_len || !flags)
-        return fail(e, CUSK_ERR_ARG, "cusk_sepselect_greedy: bad arguments");
+    const std::string who = het ? "cusk_sepselect_greedy_het" : "cusk_sepselect_greedy";
+    if (!e || !trait_corr || n <= 0 || p <= 0 || npairs < 0 || !cand_off || (het ? !trait_n : !thr) || !sel_len || !flags)
+        return fail(e, CUSK_ERR_ARG, who + ": bad arguments");
+    if (het)
+    {  // the kernel reads the size of (s, t) at either order, as it reads the correlations
+        if (n < p) return fail(e, CUSK_ERR_ARG, who + ": fewer variables than traits");
+        for (int a = 0; a < p; a++)
+            for (int c = a + 1; c < p; c++)
+                if (trait_n[(size_t)a * p + c] != trait_n[(size_t)c * p + a])
+                    return fail(e, CUSK_ERR_ARG, who + ": trait_n is not symmetric on the trait x trait block");
+    }
     if (kernel_ms) *kernel_ms = 0.0f;
     if (npairs == 0) return CUSK_OK;
-    if (!pair_i || !pair_j || !pair_corr) return fail(e, CUSK_ERR_ARG, "cusk_sepselect_greedy: bad arguments");
+    if (!pair_i || !pair_j || !pair_corr || (het && !pair_n)) return fail(e, CUSK_ERR_ARG, who + ": bad arguments");
     const long long total = cand_off[npairs];
-    if (total > 0 && (!cand || !sel)) return fail(e, CUSK_ERR_ARG, "cusk_sepselect_greedy: bad arguments");
+    if (total > 0 && (!cand || !sel)) return fail(e, CUSK_ERR_ARG, who + ": bad arguments");
     // shape checks on the host: every index the kernel forms stays inside the buffers it was given
     int max_t = 0;
     std::vector<std::vector<int>> lists(kSepLdsClasses + 1);
     for (long long k = 0; k < npairs; k++)
     {
         const long long t = cand_off[k + 1] - cand_off[k];
-        if (t < 0 || t > p || cand_off[k] < 0) return fail(e, CUSK_ERR_ARG, "cusk_sepselect_greedy: bad candidate offsets");
+        if (t < 0 || t > p || cand_off[k] < 0) return fail(e, CUSK_ERR_ARG, who + ": bad candidate offsets");
         if (pair_i[k] < 0 || pair_i[k] >= n || pair_j[k] < 0 || pair_j[k] >= n)
-            return fail(e, CUSK_ERR_ARG, "cusk_sepselect_greedy: pair index out of range");
+            return fail(e, CUSK_ERR_ARG, who + ": pair index out of range");
         max_t = std::max(max_t, (int)t);
         int c = 0;
         while (c < kSepLdsClasses && t > kSepCaps[c]) c++;
         lists[c].push_back((int)k);
     }
-    if (nthr < max_t + 1) return fail(e, CUSK_ERR_ARG, "cusk_sepselect_greedy: threshold table shorter than the longest candidate list");
+    if (!het && nthr < max_t + 1) return fail(e, CUSK_ERR_ARG, who + ": threshold table shorter than the longest candidate list");
     for (long long k = 0; k < total; k++)
-        if (cand[k] < 0 || cand[k] >= p) return fail(e, CUSK_ERR_ARG, "cusk_sepselect_greedy: candidate is not a trait index");
+        if (cand[k] < 0 || cand[k] >= p) return fail(e, CUSK_ERR_ARG, who + ": candidate is not a trait index");
 
     CUSK_HIP(e, hipSetDevice(e->device));
     hipStream_t s = e->stream;
-    DevBuf d_tc, d_pi, d_pj, d_pc, d_off, d_cand, d_thr, d_sel, d_len, d_flags, d_list, d_ws;
+    DevBuf d_tc, d_pi, d_pj, d_pc, d_off, d_cand, d_thr, d_tn, d_pn, d_sel, d_len, d_flags, d_list, d_ws;
     auto up = [&](DevBuf &b, const void *src, size_t bytes) -> hipError_t {
         hipError_t st = b.ensure(std::max<size_t>(bytes, 8));
         if (st != hipSuccess || bytes == 0) return st;
@@ -232,7 +273,13 @@ int sepselect_greedy_impl(cusk_engine *e, const double *trait_corr, long long n,
     CUSK_HIP(e, up(d_pc, pair_corr, sizeof(double) * (size_t)npairs));
     CUSK_HIP(e, up(d_off, cand_off, sizeof(long long) * (size_t)(npairs + 1)));
     CUSK_HIP(e, up(d_cand, cand, sizeof(int) * (size_t)total));
-    CUSK_HIP(e, up(d_thr, thr, sizeof(double) * (size_t)nthr));
+    if (het)
+    {
+        CUSK_HIP(e, up(d_tn, trait_n, sizeof(int) * (size_t)n * p));
+        CUSK_HIP(e, up(d_pn, pair_n, sizeof(int) * (size_t)npairs));
+    }
+    else
+        CUSK_HIP(e, up(d_thr, thr, sizeof(double) * (size_t)nthr));
     CUSK_HIP(e, d_sel.ensure(std::max<size_t>(sizeof(int) * (size_t)total, 8)));
     CUSK_HIP(e, d_len.ensure(sizeof(int) * (size_t)npairs));
     CUSK_HIP(e, d_flags.ensure(sizeof(int) * (size_t)npairs));
@@ -262,11 +309,16 @@ int sepselect_greedy_impl(cusk_engine *e, const double *trait_corr, long long n,
     b.cand_off = d_off.as<long long>();
     b.cand = d_cand.as<int>();
     b.thr = d_thr.as<double>();
+    b.tn = d_tn.as<int>();
+    b.pair_n = d_pn.as<int>();
+    b.q = q;
     b.sel = d_sel.as<int>();
     b.sel_len = d_len.as<int>();
     b.flags = d_flags.as<int>();
     b.ws = d_ws.as<double>();
     b.ws_stride = (long long)(big_bytes / sizeof(double));
+    void (*const k_lds)(SepBatch, int) = het ? sepselect_kernel<true, true> : sepselect_kernel<true, false>;
+    void (*const k_hbm)(SepBatch, int) = het ? sepselect_kernel<false, true> : sepselect_kernel<false, false>;
     hipEvent_t ev0, ev1;
     CUSK_HIP(e, hipEventCreate(&ev0));
     CUSK_HIP(e, hipEventCreate(&ev1));
@@ -280,16 +332,16 @@ int sepselect_greedy_impl(cusk_engine *e, const double *trait_corr, long long n,
         {
             const size_t lds = sep_bytes(kSepCaps[c]);
             if (lds > 48 * 1024)
-                CUSK_HIP(e, hipFuncSetAttribute(reinterpret_cast<const void *>(&sepselect_kernel<true>),
+                CUSK_HIP(e, hipFuncSetAttribute(reinterpret_cast<const void *>(k_lds),
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(sepselect_kernel<true>, dim3((unsigned)cnt), dim3(64), lds, s, b, kSepCaps[c]);
+            hipLaunchKernelGGL(k_lds, dim3((unsigned)cnt), dim3(64), lds, s, b, kSepCaps[c]);
         }
         else
         {
             for (size_t done = 0; done < cnt; done += big_batch)
             {  // same stream: a batch reuses the work space after the previous one has finished
                 b.list = d_list.as<int>() + first[c] + done;
-                hipLaunchKernelGGL(sepselect_kernel<false>, dim3((unsigned)std::min(big_batch, cnt - done)), dim3(64), 0, s, b,
+                hipLaunchKernelGGL(k_hbm, dim3((unsigned)std::min(big_batch, cnt - done)), dim3(64), 0, s, b,
                                    max_t);
             }
         }
@@ -305,7 +357,7 @@ int sepselect_greedy_impl(cusk_engine *e, const double *trait_corr, long long n,
     if (kernel_ms) *kernel_ms = ms;
     (void)hipEventDestroy(ev0);
     (void)hipEventDestroy(ev1);
-    for (DevBuf *d : {&d_tc, &d_pi, &d_pj, &d_pc, &d_off, &d_cand, &d_thr, &d_sel, &d_len, &d_flags, &d_list, &d_ws}) d->release();
+    for (DevBuf *d : {&d_tc, &d_pi, &d_pj, &d_pc, &d_off, &d_cand, &d_thr, &d_tn, &d_pn, &d_sel, &d_len, &d_flags, &d_list, &d_ws}) d->release();
     return CUSK_OK;
 }
 
@@ -316,6 +368,15 @@ extern "C" int cusk_sepselect_greedy(cusk_engine *e, const double *trait_corr, l
                                      const int *cand, const double *thr, int nthr, int *sel, int *sel_len, int *flags,
                                      float *kernel_ms)
 {
-    return cusk::sepselect_greedy_impl(e, trait_corr, n, p, npairs, pair_i, pair_j, pair_corr, cand_off, cand, thr, nthr, sel,
-                                       sel_len, flags, kernel_ms);
+    return cusk::sepselect_greedy_impl(e, trait_corr, n, p, npairs, pair_i, pair_j, pair_corr, cand_off, cand, thr, nthr, false,
+                                       nullptr, nullptr, 0.0, sel, sel_len, flags, kernel_ms);
+}
+
+extern "C" int cusk_sepselect_greedy_het(cusk_engine *e, const double *trait_corr, long long n, int p, long long npairs,
+                                         const int *pair_i, const int *pair_j, const double *pair_corr, const long long *cand_off,
+                                         const int *cand, const int *trait_n, const int *pair_n, double q, int *sel, int *sel_len,
+                                         int *flags, float *kernel_ms)
+{
+    return cusk::sepselect_greedy_impl(e, trait_corr, n, p, npairs, pair_i, pair_j, pair_corr, cand_off, cand, nullptr, 0, true,
+                                       trait_n, pair_n, q, sel, sel_len, flags, kernel_ms);
 }

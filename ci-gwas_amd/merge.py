@@ -14,6 +14,9 @@ which the merge rules below reproduce:
     overwritten by each block like marker links; everything else is taken from the block;
   * correlations (`_scm`): later blocks overwrite (the trait-trait entries are the same in every block);
   * `.ixs`: global (.bim row) index of every selected marker = index inside its block + markers of all blocks before.
+Not in the reference: a heterogeneous `cuskss` run also writes `cuskss_merged.ess`, the per-pair sample sizes in the
+layout of `.corr`; the post-step turns it into `cuskss_merged_ssz.mtx` through the same index mapping and writer as
+`_scm.mtx` (`sepselect --het` reads it).
 """
 from __future__ import annotations
 
@@ -45,9 +48,12 @@ def _dense_to_sparse_index(num_m: int, num_p: int, marker_offset: int) -> np.nda
     return np.where(ix < num_m, ix + marker_offset + num_p + BASE_INDEX, ix - num_m + BASE_INDEX)
 
 
-def _sparse_entries(path: str, n: int, to_sparse: np.ndarray, dtype):
-    """non-zero entries of a dense n x n file in row-major order: [((i, j), value), ...] in merged indices"""
+def _sparse_entries(path: str, n: int, to_sparse: np.ndarray, dtype, fix=None):
+    """non-zero entries of a dense n x n file in row-major order: [((i, j), value), ...] in merged indices; `fix` is
+    applied to the dense matrix first"""
     dm = np.fromfile(path, dtype=dtype).reshape(n, n)
+    if fix is not None:
+        dm = fix(dm)
     r, c = np.nonzero(dm)
     return [((int(i), int(j)), v) for i, j, v in zip(to_sparse[r], to_sparse[c], dm[r, c])]
 
@@ -60,6 +66,7 @@ class MergedSkeleton:
     num_var: int
     num_phen: int
     max_level: int
+    ssz: dict | None = None  # per-pair sample sizes of a heterogeneous cuskss run
 
     def write_mm(self, basepath: str) -> None:
         dim = max(k[0] for k in self.sam)  # both headers carry the adjacency's largest row index
@@ -71,6 +78,11 @@ class MergedSkeleton:
             f.write("%%MatrixMarket matrix coordinate real general\n")
             f.write(f"{dim}\t{dim}\t{len(self.scm)}\n")
             f.write("".join(f"{i}\t{j}\t{v}\n" for (i, j), v in self.scm.items()))
+        if self.ssz is not None:
+            with open(basepath + "_ssz.mtx", "w") as f:
+                f.write("%%MatrixMarket matrix coordinate real general\n")
+                f.write(f"{dim}\t{dim}\t{len(self.ssz)}\n")
+                f.write("".join(f"{i}\t{j}\t{v}\n" for (i, j), v in self.ssz.items()))
         with open(basepath + ".mdim", "w") as f:
             f.write(f"{self.num_var}\t{self.num_phen}\t{self.max_level}\n")
         np.array(sorted(self.gmi.values()), dtype=np.int32).tofile(basepath + ".ixs")
@@ -130,6 +142,11 @@ def reformat_cuskss_merged_output(cusk_dir: str) -> MergedSkeleton:
     glob = old_global[ixs[:-num_p]]
     to_sparse = _dense_to_sparse_index(num_m, num_p, 0)
     base = f"{cusk_dir}/cuskss_merged"
+    ssz = None
+    if os.path.exists(base + ".ess"):
+        # the sizes as the sweep used them: truncated to whole individuals (the se -> size chain of the loaders lands in
+        # [count, count + 1)), NaN (no size: a trait with itself, a NaN correlation) -> 0 = no entry
+        ssz = dict(_sparse_entries(base + ".ess", num_var, to_sparse, np.float32, lambda dm: np.trunc(np.nan_to_num(dm, nan=0.0))))
     return MergedSkeleton(dict(_sparse_entries(base + ".adj", num_var, to_sparse, np.int32)),
                           dict(_sparse_entries(base + ".corr", num_var, to_sparse, np.float32)),
-                          {k: v for k, v in enumerate(glob)}, num_var, num_p, max_level)
+                          {k: v for k, v in enumerate(glob)}, num_var, num_p, max_level, ssz)

@@ -20,9 +20,13 @@ were written by the reference itself):
 Deliberate deviations: dense num_var x num_var x max_level sepset arrays are not materialised (dicts are kept,
 `maximal_sepset_arr` builds the dense form on request), and `to_file` after plain `sepselect_merged` (no PAG)
 writes every other file and skips `_spm.mtx`, where the reference's writer stops with an exception (:550).
+Not in the reference: `het=True` takes every decision at the sample size of the variables it is about, read from
+`<stem>_ssz.mtx` (the post-step of a heterogeneous `cuskss-merged` run writes it), through `cusk_sepselect_greedy_het`;
+`num_samples` is not used then.  The rule is in include/cusk_hip.h and DESIGN.md section 9.
 """
 from __future__ import annotations
 
+import os
 import sys
 
 import numpy as np
@@ -40,9 +44,13 @@ def alpha_thr(alpha: float, n: int, l):
 class MergedCuskResults:
     """A merged cusk skeleton (`<stem>.mdim`, `.ixs`, `_sam.mtx`, `_scm.mtx`) and what sepselect derives from it."""
 
-    def __init__(self, stem: str, orientation_prior_file=None, device: int = 0, engine: Engine | None = None):
+    def __init__(self, stem: str, orientation_prior_file=None, device: int = 0, engine: Engine | None = None,
+                 het: bool = False):
         from scipy.io import mmread
 
+        if het and not os.path.exists(f"{stem}_ssz.mtx"):
+            raise FileNotFoundError(f"{stem}_ssz.mtx is missing: --het needs the per-pair sample sizes that "
+                                    "`cuskss-merged --het` (or cuskss with --mxp-se/--pxp-se) writes beside the skeleton")
         with open(f"{stem}.mdim") as fin:
             self.num_var, self.num_phen, self.max_level = (int(e) for e in next(fin).split())
         self.num_m = self.num_var - self.num_phen
@@ -50,6 +58,11 @@ class MergedCuskResults:
         self.adj = mmread(f"{stem}_sam.mtx").toarray().astype(bool)
         self.corr = np.asarray(mmread(f"{stem}_scm.mtx").toarray(), dtype=np.float64)
         np.fill_diagonal(self.corr, 1.0)
+        self.ssz = None  # per-pair sample sizes, entries without a size = 0
+        if os.path.exists(f"{stem}_ssz.mtx"):
+            self.ssz = np.nan_to_num(np.asarray(mmread(f"{stem}_ssz.mtx").toarray(), dtype=np.float64), nan=0.0)
+            if self.ssz.shape != self.corr.shape:
+                raise ValueError(f"{stem}_ssz.mtx and {stem}_scm.mtx differ in shape")
         self.max_sepsets = None
         self.min_sepsets = None
         self.max_level_maximal_sepsets = None
@@ -86,6 +99,8 @@ class MergedCuskResults:
         if n_rm:
             self.corr = np.ascontiguousarray(self.corr[np.ix_(keep, keep)])
             self.adj = np.ascontiguousarray(self.adj[np.ix_(keep, keep)])
+            if self.ssz is not None:
+                self.ssz = np.ascontiguousarray(self.ssz[np.ix_(keep, keep)])
             self.ixs = self.ixs[keep[p:]]
             self.num_var -= n_rm
         print(f"Removed {n_rm} collinear markers")
@@ -142,9 +157,14 @@ class MergedCuskResults:
         return pairs
 
     # ---- the hot loop: one batched device launch ----
-    def find_maximal_and_min_pcorr_sepsets_incr(self, alpha: float, num_samples: int):
-        """:262-329 for every sRFCI-relevant outer pair, on the device"""
+    def find_maximal_and_min_pcorr_sepsets_incr(self, alpha: float, num_samples: int, het: bool = False):
+        """:262-329 for every sRFCI-relevant outer pair, on the device; `het`: at the sample sizes of `self.ssz`"""
         p = self.num_phen
+        if het:
+            if self.ssz is None:
+                raise ValueError("sepselect: het=True needs the per-pair sample sizes (<stem>_ssz.mtx)")
+            if not np.array_equal(self.ssz[:, :p], self.ssz[:p, :].T):
+                raise ValueError("sepselect: the sample sizes are not symmetric on their trait rows / columns")
         if not np.array_equal(self.corr[:, :p], self.corr[:p, :].T):
             raise ValueError("sepselect: the correlation matrix is not symmetric on its trait rows / columns")
         pairs = sorted(self.get_rfci_relevant_unshielded_triples_outer_pairs())
@@ -159,11 +179,18 @@ class MergedCuskResults:
         cand_off = np.zeros(len(pairs) + 1, dtype=np.int64)
         np.cumsum(sizes, out=cand_off[1:])
         cand = np.concatenate([order[i] for i in pair_i.tolist()]) if len(pairs) else np.zeros(0, np.int32)
-        thr = alpha_thr(alpha, num_samples, np.arange(int(sizes.max()) + 1 if len(sizes) else 1, dtype=np.float64))
         if self._engine is None:
             self._engine = Engine(self._device)
-        sel, sel_len, flags, self.kernel_ms = self._engine.sepselect_greedy(
-            np.ascontiguousarray(self.corr[:, :p]), pair_i, pair_j, self.corr[pair_i, pair_j], cand_off, cand, thr)
+        if het:
+            from scipy.stats import norm
+
+            sel, sel_len, flags, self.kernel_ms = self._engine.sepselect_greedy_het(
+                np.ascontiguousarray(self.corr[:, :p]), pair_i, pair_j, self.corr[pair_i, pair_j], cand_off, cand,
+                self.ssz[:, :p].astype(np.int32), self.ssz[pair_i, pair_j].astype(np.int32), norm.ppf(1 - (alpha / 2)))
+        else:
+            thr = alpha_thr(alpha, num_samples, np.arange(int(sizes.max()) + 1 if len(sizes) else 1, dtype=np.float64))
+            sel, sel_len, flags, self.kernel_ms = self._engine.sepselect_greedy(
+                np.ascontiguousarray(self.corr[:, :p]), pair_i, pair_j, self.corr[pair_i, pair_j], cand_off, cand, thr)
         status = flags >> 8
         if np.any(status == 2):
             k = int(np.flatnonzero(status == 2)[0])
@@ -208,12 +235,12 @@ class MergedCuskResults:
                 if t[1] in self.max_sepsets.get((t[0], t[2]), ()) and t[1] not in self.min_sepsets.get((t[0], t[2]), ())]
         self.ambiguous_triples = np.array(rows, dtype=np.int32)
 
-    def orient_v_structures(self, alpha: float, num_samples: int):
+    def orient_v_structures(self, alpha: float, num_samples: int, het: bool = False):
         """:482-508 -- PAG marks 1 (adjacent), 2 (arrowhead), 3 (tail)"""
         self.pag = np.zeros(self.adj.shape, dtype=np.int32)
         self.pag[self.adj] = 1
         if self.max_sepsets is None:
-            self.find_maximal_and_min_pcorr_sepsets_incr(alpha, num_samples)
+            self.find_maximal_and_min_pcorr_sepsets_incr(alpha, num_samples, het=het)
         prior = self.orientation_prior
         for x, y, z in self.get_rfci_relevant_unshielded_triples().tolist():
             collider = y not in self.max_sepsets[(x, z)] and y not in self.max_sepsets[(z, x)]
@@ -255,19 +282,20 @@ class MergedCuskResults:
 
 
 def orient_v_structures_merged(cusk1_result_stem: str, alpha: float, num_samples: int, orientation_prior_file=None,
-                               device: int = 0) -> MergedCuskResults:
-    """:571-578"""
-    cr = MergedCuskResults(cusk1_result_stem, orientation_prior_file=orientation_prior_file, device=device)
+                               device: int = 0, het: bool = False) -> MergedCuskResults:
+    """:571-578; het: per-pair sample sizes from <stem>_ssz.mtx instead of num_samples"""
+    cr = MergedCuskResults(cusk1_result_stem, orientation_prior_file=orientation_prior_file, device=device, het=het)
     print("Orienting v-structures")
-    cr.orient_v_structures(alpha=alpha, num_samples=num_samples)
+    cr.orient_v_structures(alpha=alpha, num_samples=num_samples, het=het)
     cr.mark_ambiguous_triples()
     return cr
 
 
-def sepselect_merged(cusk1_result_stem: str, alpha: float, num_samples: int, device: int = 0) -> MergedCuskResults:
-    """:581-588"""
-    cr = MergedCuskResults(cusk1_result_stem, device=device)
+def sepselect_merged(cusk1_result_stem: str, alpha: float, num_samples: int, device: int = 0,
+                     het: bool = False) -> MergedCuskResults:
+    """:581-588; het: per-pair sample sizes from <stem>_ssz.mtx instead of num_samples"""
+    cr = MergedCuskResults(cusk1_result_stem, device=device, het=het)
     print("Starting sepselect")
-    cr.find_maximal_and_min_pcorr_sepsets_incr(alpha, num_samples)
+    cr.find_maximal_and_min_pcorr_sepsets_incr(alpha, num_samples, het=het)
     cr.mark_ambiguous_triples()
     return cr

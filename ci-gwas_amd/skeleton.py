@@ -438,6 +438,31 @@ class Engine:
                                                 _ptr(sel), _ptr(sel_len), _ptr(flags), _ptr(ms)))
         return sel, sel_len[:npairs], flags[:npairs], float(ms[0])
 
+    def sepselect_greedy_het(self, trait_corr, pair_i, pair_j, pair_corr, cand_off, cand, trait_n, pair_n, q):
+        """`sepselect_greedy` at per-pair sample sizes (cusk_sepselect_greedy_het): `trait_n` is the n x p int32 table of
+        sample sizes in the layout of `trait_corr`, `pair_n` the size of every outer pair, `q` = norm.ppf(1 - alpha / 2)."""
+        trait_corr = np.ascontiguousarray(trait_corr, np.float64)
+        n, p = trait_corr.shape
+        pair_i = np.ascontiguousarray(pair_i, np.int32)
+        pair_j = np.ascontiguousarray(pair_j, np.int32)
+        pair_corr = np.ascontiguousarray(pair_corr, np.float64)
+        cand_off = np.ascontiguousarray(cand_off, np.int64)
+        cand = np.ascontiguousarray(cand, np.int32)
+        trait_n = np.ascontiguousarray(trait_n, np.int32)
+        pair_n = np.ascontiguousarray(pair_n, np.int32)
+        npairs = pair_i.shape[0]
+        assert trait_n.shape == (n, p) and pair_n.shape[0] == npairs
+        assert pair_j.shape[0] == npairs and pair_corr.shape[0] == npairs and cand_off.shape[0] == npairs + 1
+        assert cand.shape[0] == int(cand_off[-1])
+        sel = np.full(max(cand.shape[0], 1), -1, np.int32)
+        sel_len = np.zeros(max(npairs, 1), np.int32)
+        flags = np.zeros(max(npairs, 1), np.int32)
+        ms = np.zeros(1, np.float32)
+        self._check(lib().cusk_sepselect_greedy_het(self.h, _ptr(trait_corr), n, p, npairs, _ptr(pair_i), _ptr(pair_j),
+                                                    _ptr(pair_corr), _ptr(cand_off), _ptr(cand), _ptr(trait_n), _ptr(pair_n),
+                                                    float(q), _ptr(sel), _ptr(sel_len), _ptr(flags), _ptr(ms)))
+        return sel, sel_len[:npairs], flags[:npairs], float(ms[0])
+
     def corr_timing(self):
         t = np.zeros(4, np.float32)
         lib().cusk_corr_timing(self.h, _ptr(t))

@@ -356,6 +356,24 @@ int cusk_sepselect_greedy(cusk_engine *e, const double *trait_corr, long long n,
                           const int *pair_i, const int *pair_j, const double *pair_corr, const long long *cand_off,
                           const int *cand, const double *thr, int nthr, int *sel, int *sel_len, int *flags,
                           float *kernel_ms);
+/* The same selection with every decision taken at the sample size of the variables it is about (a merged skeleton
+ * found at per-pair sample sizes: `cuskss` with se files, `cuskss-merged --het`).  Arguments and results as above, with
+ * the threshold table replaced by
+ *   trait_n     n x p int32, row-major, layout of trait_corr: the number of individuals variable v and trait t were both
+ *               observed on; must be symmetric on the trait x trait block (rows 0 .. p-1)
+ *   pair_n      pair_n[k] = that number for (pair_i[k], pair_j[k])
+ *   q           norm.ppf(1 - alpha/2)
+ * A decision over the variables V = {i, j} + S + {t}, |S + {t}| = l, is taken against q / sqrt(mean - l - 3), where
+ * mean = (sum of the sizes of all (l + 2)(l + 1) / 2 unordered pairs of V) / that count -- the mean_ess of the hetcor
+ * sweep, with a 64-bit integer sum and IEEE double division and square root.  A negative or NaN radicand gives a NaN
+ * threshold, against which the comparison is false: "not independent" (plain IEEE, nothing is special-cased).  Which
+ * candidate a round picks does not depend on the threshold.  A marker's row of trait_n is read only where the marker
+ * is i or j.  With every size equal to N the mean is exactly N and the results equal those of cusk_sepselect_greedy
+ * with the table built from N. */
+int cusk_sepselect_greedy_het(cusk_engine *e, const double *trait_corr, long long n, int p, long long npairs,
+                              const int *pair_i, const int *pair_j, const double *pair_corr, const long long *cand_off,
+                              const int *cand, const int *trait_n, const int *pair_n, double q, int *sel, int *sel_len,
+                              int *flags, float *kernel_ms);
 
 /* out_host[a*k + b] = M_dev[idx[a]*n + idx[b]]: the retained sub-matrix of parent_set.cpp:84-238
  * (reduce_gc / reduce_gcs) without copying the n*n matrix to the host; idx_host has k entries. */
