@@ -87,6 +87,7 @@ SYMBOLS = {
     "cusk_engine_destroy": (None, [_vp]),
     "cusk_last_error": (C.c_char_p, [_vp]),
     "cusk_engine_set_option": (_i, [_vp, C.c_char_p, _ll]),
+    "cusk_level1_rows_threads": (_i, [_ll, _i, _i, _i]),
     "cusk_engine_stream": (_vp, [_vp]),
     "cusk_engine_bind_thread": (_i, [_vp]),
     "cusk_engine_device": (_i, [_vp]),

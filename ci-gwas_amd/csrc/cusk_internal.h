@@ -149,7 +149,8 @@ struct cusk_engine
     long long opt_item_cap = 1ll << 20;  // work items per degree class and level the buffers hold before they are grown
     int opt_lookahead = 2;               // levels the host may enqueue ahead of the counters it has seen
     int opt_sync2 = 1;                   // the host reads level 2's gate record before it enqueues that level's sweeps (engine.hip)
-    int opt_l1_exp = 0;                  // level-1 row kernel experiment bits (sweep_level.hip: RowsParams::exp)
+    int opt_l1_threads = 0;              // test hook: 256 / 512 forces that workgroup size of level1_rows2_kernel (0: level1_rows_threads chooses)
+    int opt_l1_lds_row = 1;              // test hook: 0 forces the form of level1_rows2_kernel that gathers the row of C through L1/L2
     int opt_timing = 1;                  // per-level HIP events for cusk_stats' kernel_ms / level_ms (0: total only)
     long long opt_sep_ws_budget = 4ll << 30;  // HBM work space of cusk_sepselect_greedy for candidate lists beyond LDS
 

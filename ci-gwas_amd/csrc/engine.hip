@@ -226,7 +226,7 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
         {
             CUSK_HIP(e, launch_level1_rows(a.mode, e->opt_validate != 0, pl.filter_ok && e->opt_fast != 0, sp, e->rv.as<float>(),
                                            e->rpos.p, e->sel.as<unsigned>(), e->wpre.as<int>(), e->opt_timing ? e->ev_main[0] : nullptr,
-                                           e->opt_timing ? e->ev_main[1] : nullptr, e->shard_rank, e->shard_world, e->opt_l1_exp, sharded,
+                                           e->opt_timing ? e->ev_main[1] : nullptr, e->shard_rank, e->shard_world, e->opt_l1_threads, e->opt_l1_lds_row != 0, sharded,
                                            a.time_index != nullptr, (a.mode == 1) ? dcanon + (size_t)l * kCounterSlots : nullptr, s));
             rows_timed = true;
             return CUSK_OK;
@@ -986,8 +986,10 @@ extern "C" int cusk_engine_set_option(cusk_engine *e, const char *key, long long
         e->opt_lookahead = (int)value;
     else if (k == "timing")
         e->opt_timing = (int)value;
-    else if (k == "l1_exp")
-        e->opt_l1_exp = (int)value;
+    else if (k == "l1_threads" && (value == 0 || value == 256 || value == 512))
+        e->opt_l1_threads = (int)value;
+    else if (k == "l1_lds_row" && (value == 0 || value == 1))
+        e->opt_l1_lds_row = (int)value;
     else if (k == "sync2")
         e->opt_sync2 = (int)value;
     else if (k == "sepselect_ws_bytes" && value > 0)

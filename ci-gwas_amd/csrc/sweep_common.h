@@ -264,7 +264,7 @@ hipError_t launch_sweep_vec(int mode, int L, const SweepParams &p, int cls, int 
 // workgroups of a persistent sweep launch: what the chip holds at once for this kernel (occupancy x CUs), cached
 unsigned persistent_grid(const void *kernel, int threads, size_t lds);
 size_t sweep_vec_lds_bytes(int cls);
-// sweep_level.hip: level 0, compaction, level-1 pair kernel, result expansion
+// level0.hip, plan.hip, level1.hip, readout.hip: level 0, compaction and plan, level 1, result expansion
 hipError_t launch_level0(const float *C, const float *Ness, const int *Ginit, unsigned long long *adj, int n, int words,
                          float th, int *asym_flag, hipStream_t st);
 // block-diagonal level 0 of a batched Skeleton run: adjacency words of every row inside its block's column range, zeros
@@ -304,7 +304,8 @@ hipError_t launch_expand_records(const int *rec_s, const int *rec_l, long long r
                                  hipStream_t st);
 hipError_t launch_level1_rows(int mode, bool validate, bool use_filter, const SweepParams &p, float *rv, void *meta,
                               unsigned *sel, const int *wpre, hipEvent_t ev_begin, hipEvent_t ev_end, int shard_rank,
-                              int shard_world, int exp, bool defer_apply, bool has_ti, unsigned long long *canon, hipStream_t st);
+                              int shard_world, int force_threads, bool lds_row, bool defer_apply, bool has_ti,
+                              unsigned long long *canon, hipStream_t st);
 // hetcor mode, row-sharded runs: adjacency bitmap -> per-slot marks (0 gone / all ones alive), and back after the join
 hipError_t launch_marks_from_bitmap(const SweepParams &p, unsigned *sel, hipStream_t st);
 hipError_t launch_level1_apply(const SweepParams &p, const unsigned *sel, const void *meta, bool count_removed, hipStream_t st);

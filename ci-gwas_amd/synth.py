@@ -668,3 +668,29 @@ DISPATCH_CASES = {
     "l4": (4, (39, 40, 63, 64)),
     "l5": (5, (39, 40, 41)),
 }
+
+
+def level1_star_case(n: int = 1301, hub: int = 3, seed: int = 1, N: int = 4096, alpha: float = 1e-4, pairs: int = 256):
+    """Population correlation matrix (float32) of a star for the level-1 row kernel: one hub row with n - 1 neighbours
+    at the start of level 1 (more than two staging rounds of a 512-thread workgroup), child rows of every degree up to
+    about 0.6 n, and a level 1 that removes most of what level 0 left.
+
+    One factor: C[hub, c_k] = rho_k and C[c_j, c_k] = rho_j rho_k, so the hub separates every pair of children exactly.
+    rho_k runs from 0.5 down to 0.08 (denser at the low end, shuffled over the indices), so rho_j rho_k straddles
+    tanh(Th[0]) and level 0 keeps the child-child edges with the larger products.  `pairs` disjoint pairs of children
+    with rho >= 0.2 get a partial correlation e in [0.15, 0.3] given the hub on top (C += e sqrt((1 - rho_j^2)
+    (1 - rho_k^2))): those edges survive level 1.  n is not a multiple of 4 (the 16-byte row staging clamps its last
+    piece).  Returns (Cm, info) with info["hub"], "N", "alpha", "rho" and the perturbed "pairs"."""
+    rng = np.random.default_rng(seed)
+    kids = np.array([v for v in range(n) if v != hub])
+    rho = np.zeros(n)
+    rho[kids] = rng.permutation(0.08 + 0.42 * np.linspace(0.0, 1.0, n - 1) ** 2.5)
+    rho[hub] = 1.0
+    Cm = np.outer(rho, rho)
+    strong = rng.permutation(kids[rho[kids] >= 0.2])[: 2 * pairs].reshape(-1, 2)
+    e = rng.uniform(0.15, 0.3, len(strong))
+    for (j, k), ee in zip(strong, e):
+        Cm[j, k] = Cm[k, j] = rho[j] * rho[k] + ee * np.sqrt((1 - rho[j] ** 2) * (1 - rho[k] ** 2))
+    np.fill_diagonal(Cm, 1.0)
+    info = {"hub": hub, "N": N, "alpha": alpha, "rho": rho, "pairs": [(int(j), int(k)) for j, k in strong]}
+    return np.ascontiguousarray(Cm.astype(np.float32)), info

@@ -68,3 +68,58 @@ def test_comb_rank_is_the_oracles_enumeration(oracle, synth):
             T = synth.comb_unrank(r, d, l)
             assert synth.comb_rank(T, d) == r
             assert list(oracle.ith_combination(d, l, r + 1) - 1) == T
+
+
+def test_level1_star_case_reaches_the_staging_rounds(oracle, synth):
+    """the input of tests/test_gpu_level1_forms.py: one row with more than two 512-neighbour staging rounds at the start
+    of level 1, rows in both degree ranges between the workgroup sizes, and a level 1 that removes most edges and keeps
+    some between non-hub rows"""
+    Cm, info = synth.level1_star_case()
+    n, hub = Cm.shape[0], info["hub"]
+    assert n % 4 != 0 and np.array_equal(Cm, Cm.T)
+    Th = oracle.threshold_array(info["N"], info["alpha"])
+    G0, G1 = oracle.skeleton(Cm, Th, 0).G, oracle.skeleton(Cm, Th, 1).G
+    deg = G0.sum(1)
+    assert deg[hub] >= 1030
+    others = np.delete(deg, hub)
+    assert ((others > 256) & (others <= 512)).sum() >= 3 and ((others > 512) & (others <= 1024)).sum() >= 3
+    assert (G0.sum() - G1.sum()) // 2 >= 1000
+    rest = np.arange(n) != hub
+    assert G1[np.ix_(rest, rest)].sum() // 2 >= 100
+
+
+def _parent_rows_threads(row_lds, mode, validate):
+    """the launcher's loop over the candidate sizes as it stood before level1_rows_threads (no size forced)"""
+    threads = best_wgs = best_waves = 0
+    for t in (256, 512):
+        fixed = 16 * t + 4 * (2 * t + 1) + 4 * 2 * (t // 64) + 64
+        wgs = min(160 * 1024 // (row_lds + fixed), (16 if (mode == 0 and not validate) else 12) // (t // 64))
+        waves = wgs * (t // 64)
+        if wgs >= 2 and (wgs > best_wgs or (wgs == best_wgs and waves > best_waves)):
+            best_wgs, best_waves, threads = wgs, waves, t
+    return threads
+
+
+def test_level1_rows_threads_is_the_former_choice():
+    """level1_rows_threads (level1.hip) through its host-only entry: with nothing forced, the size the launcher chose
+    before for every n, mode and validate; forced, that size whenever one row fits a CU's LDS.  (A matrix that is not
+    16-byte aligned takes the gather form before the function is asked: test_gpu_level1_forms.py.)"""
+    from cigwas_amd._lib import lib
+
+    f = lib().cusk_level1_rows_threads
+    ranges = {}
+    for mode in (0, 1):
+        for validate in (0, 1):
+            got = []
+            for n in range(64, 40001, 61):
+                row = 4 * (n + 8)
+                got.append(f(row, mode, validate, 0))
+                assert got[-1] == _parent_rows_threads(row, mode, validate), (n, mode, validate)
+                for forced in (256, 512):
+                    fixed = 16 * forced + 4 * (2 * forced + 1) + 4 * 2 * (forced // 64) + 64
+                    assert f(row, mode, validate, forced) == (forced if row + fixed <= 160 * 1024 else 0)
+            ranges[(mode, validate)] = got
+    # 512 threads only for Skeleton runs that do not validate (two rows of eight waves), the gather form from n ~ 16,000
+    assert 512 in ranges[(0, 0)] and all(512 not in v for k, v in ranges.items() if k != (0, 0))
+    assert all(v[0] == 256 and v[-1] == 0 for v in ranges.values())
+    assert f(4096, 0, 0, 384) == -1 and f(-1, 0, 0, 0) == -1

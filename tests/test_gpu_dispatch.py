@@ -24,6 +24,7 @@ SKELETON_OPTS = [
     {"rows": 0}, {"pair": 0},
     SMALL, {**SMALL, "vec": 0}, {**SMALL, "tmaj_min_level": 2}, {**SMALL, "vec_threads": 256},
     {"overlap": 0}, {"sync2": 0}, {"assume_symmetric": 1},
+    {"l1_threads": 512}, {"l1_lds_row": 0}, {"l1_threads": 512, "validate": 1},
 ]
 CASES = ["l2", "l3", "l4", "l5"]
 
@@ -116,7 +117,7 @@ def test_skeleton_dispatch_matrix(cg, name, opts):
         e.close()
 
 
-@pytest.mark.parametrize("opts", [{}, {"fast": 0}, {"max_staged_classes": 0}], ids=_optid)
+@pytest.mark.parametrize("opts", [{}, {"fast": 0}, {"max_staged_classes": 0}, {"l1_threads": 512}, {"l1_lds_row": 0}], ids=_optid)
 @pytest.mark.parametrize("het,with_ti", [(False, False), (False, True), (True, False), (True, True)],
                          ids=["uniform", "uniform-ti", "het", "het-ti"])
 @pytest.mark.parametrize("name", CASES)

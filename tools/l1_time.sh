@@ -1,4 +1,4 @@
-# level-1 row kernel timing under engine options: bash tools/l1_time.sh "l1_exp=0" "l1_exp=1024" ...
+# level-1 row kernel timing under engine options: bash tools/l1_time.sh "l1_threads=0" "l1_threads=512" "l1_lds_row=0" ...
 for o in "$@"; do
   args=""; for kv in $(echo $o | tr ',' ' '); do args="$args --option $kv"; done
   python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-chromosome $args 2>/dev/null | python -c "

@@ -4,5 +4,5 @@
 for v in "$@"; do
   cp $v ci-gwas_amd/csrc/libcusk_hip.so
   echo "== $v"
-  bash tools/l1_time.sh l1_exp=0 l1_exp=0 2>&1 | cut -c 1-100
+  bash tools/l1_time.sh l1_threads=0 l1_threads=0 2>&1 | cut -c 1-100
 done
