@@ -64,6 +64,9 @@ def _add_cusk(sub):
     p.add_argument("max_level_two", metavar="max-level-two", type=TypeCheck(int, "max-level", 0, 14), default=14)
     p.add_argument("max_depth", metavar="max-depth", type=TypeCheck(int, "max-depth", 1, None), default=1)
     p.add_argument("outdir", type=str, default="./")
+    p.add_argument("--het", action="store_true",
+                   help="test every marker-trait and trait-trait pair of the block at the number of individuals it was "
+                        "observed on (phenotypes with NA entries), as `cuskss-merged --bfiles --phen --het` does afterwards")
     p.set_defaults(func=cusk)
 
 
@@ -194,7 +197,8 @@ def block(args):
 def cusk_argv(args) -> list[str]:
     """ci-gwas.py:404-420"""
     return [MPS_PATH, "cusk", args.phen, args.bfiles, args.blocks, str(args.alpha), str(args.max_level),
-            str(args.max_level_two), str(args.max_depth), args.outdir, str(args.block_index)]
+            str(args.max_level_two), str(args.max_depth), args.outdir, str(args.block_index)] + (
+                ["het"] if getattr(args, "het", False) else [])
 
 
 def sumstats_argv(args) -> list[str]:

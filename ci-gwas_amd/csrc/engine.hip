@@ -63,10 +63,10 @@ struct RunArgs
 {
     int mode;  // 0 Skeleton, 1 hetcor
     const float *C;
-    const float *Ness;      // hetcor, may be null (uniform)
+    const float *Ness;      // hetcor, may be null (uniform); Skeleton: not null = per-pair thresholds (cusk_run_skeleton_het)
     float ess_uniform;      // hetcor uniform ESS
     const int *Ginit;       // hetcor, device n*n or null
-    const float *Th;        // mode 0: host thresholds ; mode 1: Th[0] = alpha/2 quantile
+    const float *Th;        // mode 0: host thresholds ; mode 1 and mode 0 with Ness: Th[0] = alpha/2 quantile
     const int *time_index;  // host, n entries or null
     int n;
     int maxlevel;
@@ -124,7 +124,9 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
     e->nrec = 0;
     cusk_stats local;
     std::memset(&local, 0, sizeof(local));
-    const bool het = (a.mode == 1 && a.Ness != nullptr);
+    // per-pair sample sizes: hetcor with a matrix, or Skeleton's records with hetcor's thresholds (cusk_run_skeleton_het)
+    const bool het = (a.Ness != nullptr);
+    const bool het0 = het && a.mode == 0;  // exact path only: no filter, no union-major sweep, no level-1 row / pair kernels
     const int last_level = std::min(kML, a.maxlevel);
     const bool sharded = e->shard_world > 1;
     if (sharded && !e->shard_fn) return fail(e, CUSK_ERR_ARG, "row sharding needs an exchange function");
@@ -446,10 +448,10 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
             // same class (exact path, heterogeneous thresholds, levels >= kVecMaxLevel) want long runs of consecutive ranks
             {
                 float th_l;
-                if (a.mode == 0)
-                    th_l = a.Th[l];
-                else if (het)
+                if (het)
                     th_l = a.Th[0];
+                else if (a.mode == 0)
+                    th_l = a.Th[l];
                 else
                     th_l = uniform_ess_threshold(a.Th[0], a.ess_uniform, l);
                 const bool vec0 = (e->opt_fast != 0) && l >= 2 && l < kVecMaxLevel && th_l >= kThMinFilter && !het && e->opt_vec &&
@@ -562,7 +564,7 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
                 for (int c = 0; c < kNumClasses; c++) pl.nitems[c] = e->hgate[l].class_items[c];
                 pl.known_items = true;
             }
-            pl.use_fast = (e->opt_fast != 0) && (l >= 2) && !pl.force_exact;
+            pl.use_fast = (e->opt_fast != 0) && (l >= 2) && !pl.force_exact && !het0;
             // 2. the neighbour lists (no host dependency)
             CUSK_HIP(e, launch_fill_nbr(e->adj.as<unsigned long long>(), off_l, e->nbr[cs].as<int>(),
                                         (a.mode == 0 && !pl.use_rows) ? e->best[cs].as<unsigned long long>() : nullptr, n, words,
@@ -612,10 +614,10 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
             sp.row_range = a.row_range;
             sp.max_span = a.row_range ? a.max_span : n;
             sp.slots = dslots + (size_t)l * kCounterSlots * 4;
-            if (a.mode == 0)
-                sp.th = a.Th[l];
-            else if (het)
+            if (het)
                 sp.th = a.Th[0];
+            else if (a.mode == 0)
+                sp.th = a.Th[l];
             else
                 sp.th = uniform_ess_threshold(a.Th[0], a.ess_uniform, l);
             {
@@ -1212,6 +1214,29 @@ extern "C" int cusk_run_hetcor(cusk_engine *e, const float *C_dev, const float *
     float thv[1] = {th};
     a.Th = thv;
     a.time_index = time_index;
+    a.n = n;
+    a.maxlevel = maxlevel;
+    return run_levels(e, a, stats);
+}
+
+// Skeleton's outputs (lowest passing rank per slot, separating-set records, pMax) decided at hetcor's per-test thresholds.
+// The level loop is Skeleton's; every level runs on the exact path (sweep_exact.hip, MODE 0 / HET).
+extern "C" int cusk_run_skeleton_het(cusk_engine *e, const float *C_dev, const float *N_dev, int n, float th, int maxlevel,
+                                     cusk_stats *stats)
+{
+    if (!e) return CUSK_ERR_ARG;
+    if (!N_dev) return fail(e, CUSK_ERR_ARG, "cusk_run_skeleton_het: needs the sample-size matrix");
+    if (e->shard_world > 1)
+        return fail(e, CUSK_ERR_ARG, "cusk_run_skeleton_het: a row-sharded engine is not supported (per-pair sample sizes run on one engine)");
+    if (e->opt_validate)
+        return fail(e, CUSK_ERR_ARG, "cusk_run_skeleton_het: option validate is not supported (every test already runs on the exact path)");
+    e->batch_lo.clear();
+    RunArgs a{};
+    a.mode = 0;
+    a.C = C_dev;
+    a.Ness = N_dev;
+    float thv[1] = {th};
+    a.Th = thv;
     a.n = n;
     a.maxlevel = maxlevel;
     return run_levels(e, a, stats);

@@ -205,6 +205,13 @@ extern "C" int cusk_blockset_run_block_next(cusk_blockset *bs, cusk_engine *e, i
 
 extern "C" const char *cusk_blockset_last_error(void) { return g_err.c_str(); }
 
+extern "C" int cusk_blockset_set_het(cusk_blockset *bs, int het)
+{
+    if (!bs) return CUSK_ERR_ARG;
+    bs->in.het = het != 0;
+    return CUSK_OK;
+}
+
 extern "C" void cusk_blockset_release_engine(cusk_blockset *bs, cusk_engine *e)
 {
     if (!bs || !e) return;
@@ -225,6 +232,13 @@ extern "C" int cusk_blockset_run_batch(cusk_blockset *bs, cusk_engine *e, const 
 {
     if (!bs || !e || !out || !block_indices || nblocks < 0) return CUSK_ERR_ARG;
     *out = nullptr;
+    if (bs->in.het)
+    {
+        copy_err("cusk_blockset_run_batch: this block set runs at per-pair sample sizes (cusk_blockset_set_het), which the "
+                 "batched run does not support; run its blocks with cusk_blockset_run_block",
+                 nullptr, 0);
+        return CUSK_ERR_ARG;
+    }
     if (!bs->staged_of(e) && cusk_blockset_stage(bs, e) != CUSK_OK) return CUSK_ERR_HIP;
     const StagedInputs *staged = bs->staged_of(e);
     BatchScratch &scratch = bs->batch_scratch_of(e);

@@ -140,6 +140,44 @@ inline int count_significant(const float *mxp, size_t count, float th0)
     return num_sig;
 }
 
+// The prefilter of a run at per-pair sample sizes (`mps cusk ... het`): a marker-trait pair counts when its correlation is
+// not NaN and level 0 of cusk_run_skeleton_het keeps its edge.  This is the expression that kernel's verdicts are
+// certified against (level0.hip: its single-precision estimate settles an element only outside a 1e-3 band around the
+// threshold and hands everything else to this arithmetic; ci_exact.h: z_below / fisher_z_ratio), evaluated for every
+// element, so the count cannot disagree with the sweep the way a second formula with its own rounding could: a block is
+// skipped exactly when level 0 would leave no marker-trait edge with a defined correlation.  A NaN size, or one of 3 or
+// less, gives a NaN threshold or a NaN comparison: false, the edge stays, the pair counts.
+inline int count_significant_het(const float *mxp, const float *mxp_ess, size_t count, float th)
+{
+    int num_sig = 0;
+    for (size_t i = 0; i < count; i++)
+    {
+        const float c = mxp[i];
+        if (c != c) continue;
+        const float lth = (float)((double)th / std::sqrt((double)mxp_ess[i] - 3.0));
+        const float q = (1.0f + c) / (1.0f - c);
+        const float z = std::fabs(0.5f * (float)std::log((double)std::fabs(q)));
+        num_sig += !(z < lth);
+    }
+    return num_sig;
+}
+
+// The sample sizes of a block at per-pair sample sizes, as `cuskss` would load them from the files of `mps sumstats ... se`
+// and as `mps cuskss-bed ... het` forms them: the count of complete observations through the standard error such a file
+// would hold (cusk_se_from_count -> cusk_ess_from_se), NaN where the correlation is NaN and on the trait diagonal.  pxp
+// (p x p correlations) and pxp_n are read as the pxp loader reads them: the upper triangle, mirrored.
+inline void block_sample_sizes(const float *mxp, const int *mxp_n, const float *pxp, const int *pxp_n, size_t m, size_t p,
+                               std::vector<float> &mxp_ess, std::vector<float> &pxp_ess)
+{
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    auto ess_of = [&](float r, int count) { return std::isnan(r) ? nan : cusk_ess_from_se(r, cusk_se_from_count(r, count)); };
+    mxp_ess.resize(m * p);
+    pxp_ess.assign(p * p, nan);
+    for (size_t i = 0; i < m * p; i++) mxp_ess[i] = ess_of(mxp[i], mxp_n[i]);
+    for (size_t a = 0; a < p; a++)
+        for (size_t b = a + 1; b < p; b++) pxp_ess[a * p + b] = pxp_ess[b * p + a] = ess_of(pxp[a * p + b], pxp_n[a * p + b]);
+}
+
 // ReducedGC / ReducedGCS of include/mps/parent_set.h
 // One separating set of the reduced result: the cell (ix, iy) of the num_var x num_var x max_level array holds s[0 .. cnt)
 // followed by -1
@@ -416,6 +454,10 @@ struct CuskInputs
     BimInfo bim;
     std::vector<Block> blocks;
     float Th[ML + 1];
+    // `mps cusk ... het`: every pair with a trait at the number of individuals it was observed on (run_cusk_block's het
+    // branch); th_het = the alpha/2 quantile the per-test thresholds are formed from
+    bool het = false;
+    float th_het = 0.0f;
     MappedFile bed;
     // all markers' means / stds, read once when several blocks are run from one process (empty: line-range reads)
     std::vector<float> means_all, stds_all;
@@ -440,6 +482,7 @@ struct CuskInputs
             if (b.first >= bim.markers_on(b.chr) || b.last >= bim.markers_on(b.chr))
                 die("block out of bounds with first_ix: " + std::to_string(b.first) + " last_ix: " + std::to_string(b.last));
         cusk_threshold_array((int)dims.num_samples, alpha, Th);
+        th_het = cusk_hetcor_threshold(alpha);
         bed.open(bfiles + ".bed");
     }
     void load_all_marker_stats()
@@ -449,6 +492,26 @@ struct CuskInputs
     }
     size_t first_marker(const Block &b) const { return bim.start_of(b.chr) + b.first; }
 };
+
+// argv of `mps cusk` (cli.cpp:432-456 plus the optional trailing `het`): false = too few arguments (the caller prints the
+// usage text and exits with 1); an unknown trailing argument or one too many dies with a message (status 1)
+inline bool parse_cusk_args(int argc, char **argv, CuskInputs &in, std::string &outdir, int &block_index)
+{
+    if (argc < 11) return false;
+    in.phen_path = argv[2];
+    in.bfiles = argv[3];
+    in.block_path = argv[4];
+    in.alpha = std::stof(argv[5]);
+    in.max_level = std::stoi(argv[6]);
+    in.max_level_two = std::stoi(argv[7]);
+    in.depth = std::stoi(argv[8]);
+    outdir = argv[9];
+    block_index = std::stoi(argv[10]);
+    in.het = argc > 11;
+    if (in.het && std::string(argv[11]) != "het") die(std::string("cusk: unknown trailing argument ") + argv[11]);
+    if (argc > 12) die(std::string("cusk: unknown trailing argument ") + argv[12]);
+    return true;
+}
 
 // the inputs all blocks share, resident on one device (cusk_blockset_stage): marker g's genotypes start at
 // bed + g * bytes_per_col, means / stds are indexed by global marker
@@ -478,12 +541,15 @@ struct BlockStats
     // wall-clock phases, ms: inputs (bed slice, means, stds), correlation build, stage one, prune + gather,
     // stage two, reduction
     double ms_inputs = 0, ms_corr = 0, ms_stage1 = 0, ms_prune = 0, ms_stage2 = 0, ms_reduce = 0;
+    // het runs, both part of ms_corr: the count pass (cusk_pair_counts), and the size chain on the host + cusk_ess_square
+    double ms_counts = 0, ms_ess = 0;
 };
 
 // per-caller device scratch that survives from block to block
 struct BlockScratch
 {
     DevMat C, C2;
+    DevMat Ness, Ness2;  // het runs: the sample-size matrices of the block and of its stage-two set
     // the NEXT block's correlation matrix, being built on the engine's third stream while this block is swept
     // (cusk_corr_build_begin / _end): pending >= 0 = its block index, pending_m = its marker count
     DevMat Cnext;
@@ -560,7 +626,7 @@ inline bool run_cusk_block(cusk_engine *e, const CuskInputs &in, int block_index
         *log << "Checking for significant marker - phen correlations" << std::endl;
         *log << "Computing all correlations" << std::endl;
     }
-    std::vector<float> mxp(m * p);
+    std::vector<float> mxp(m * p), mxp_ess, pxp_ess;
     if (scr.pending == block_index && scr.pending_m == m)
     {  // built ahead, beside the previous block's sweeps
         scr.pending = -1;
@@ -593,8 +659,26 @@ inline bool run_cusk_block(cusk_engine *e, const CuskInputs &in, int block_index
         }
     }
     bs.ms_corr = ms_since(t);
+    if (in.het && p > 0)
+    {
+        // Per-pair sample sizes: complete-observation counts of every marker x trait and trait x trait pair of the block
+        // (resident inputs when staged; a correlation build started ahead runs on its own stream and buffers), the sizes
+        // `cuskss-merged --het` gives the same pairs, and their expansion to the n x n matrix on the device.
+        std::vector<int> mxp_n(m * p), pxp_n(p * p);
+        if (cusk_pair_counts(e, bed, phen, nullptr, m, m, N, p, mxp_n.data(), pxp_n.data()) != CUSK_OK) engine_die("pair counts", e);
+        bs.ms_counts = ms_since(t);
+        std::vector<int> traits(p);
+        std::iota(traits.begin(), traits.end(), (int)m);
+        const std::vector<float> pxp = gather(e, scr.C.p, (int)n, traits);
+        block_sample_sizes(mxp.data(), mxp_n.data(), pxp.data(), pxp_n.data(), m, p, mxp_ess, pxp_ess);
+        scr.Ness.reserve(n * n);
+        if (cusk_ess_square(e, mxp_ess.data(), pxp_ess.data(), m, p, (float)N, scr.Ness.p) != CUSK_OK) engine_die("sample-size matrix", e);
+        bs.ms_ess = ms_since(t);
+        bs.ms_corr += bs.ms_counts + bs.ms_ess;
+    }
     // cli.cpp:561-576: blocks without any marginally significant marker-trait correlation are skipped
-    const int num_sig = count_significant(mxp.data(), mxp.size(), in.Th[0]);
+    const int num_sig = in.het ? count_significant_het(mxp.data(), mxp_ess.data(), mxp.size(), in.th_het)
+                               : count_significant(mxp.data(), mxp.size(), in.Th[0]);
     bs.num_sig = num_sig;
     if (num_sig > 0)
     {
@@ -616,7 +700,12 @@ inline bool run_cusk_block(cusk_engine *e, const CuskInputs &in, int block_index
     if (log) *log << "Running cuPC" << std::endl;
     cusk_engine_set_option(e, "assume_symmetric", 1);  // cusk_corr_build mirrors every element
     cusk_stats &st = bs.stage[0];
-    if (cusk_run_skeleton(e, scr.C.p, (int)n, in.Th, in.max_level, &st) != CUSK_OK) engine_die("Skeleton", e);
+    if (in.het)
+    {
+        if (cusk_run_skeleton_het(e, scr.C.p, scr.Ness.p, (int)n, in.th_het, in.max_level, &st) != CUSK_OK) engine_die("Skeleton (het)", e);
+    }
+    else if (cusk_run_skeleton(e, scr.C.p, (int)n, in.Th, in.max_level, &st) != CUSK_OK)
+        engine_die("Skeleton", e);
     bs.ms_stage1 = ms_since(t);
     for (int l = 0; l < st.levels_run; l++)
     {
@@ -649,6 +738,11 @@ inline bool run_cusk_block(cusk_engine *e, const CuskInputs &in, int block_index
     const int k = (int)gcs.num_var;
     scr.C2.reserve((size_t)k * k);
     if (cusk_gather_submatrix_dev(e, scr.C.p, (int)n, P.data(), k, scr.C2.p) != CUSK_OK) engine_die("gather", e);
+    if (in.het)
+    {  // the sizes of the retained variables, by the same index list
+        scr.Ness2.reserve((size_t)k * k);
+        if (cusk_gather_submatrix_dev(e, scr.Ness.p, (int)n, P.data(), k, scr.Ness2.p) != CUSK_OK) engine_die("gather (sizes)", e);
+    }
     bs.ms_prune = ms_since(t);
     // (the stage-one separating sets of cli.cpp:673 are never read again: stage two recomputes them)
 
@@ -656,7 +750,13 @@ inline bool run_cusk_block(cusk_engine *e, const CuskInputs &in, int block_index
     // Skeleton again on the reduced set, starting from the complete graph
     cusk_engine_set_option(e, "assume_symmetric", 0);
     cusk_stats &st2 = bs.stage[1];
-    if (cusk_run_skeleton(e, scr.C2.p, k, in.Th, in.max_level_two, &st2) != CUSK_OK) engine_die("Skeleton (stage two)", e);
+    if (in.het)
+    {
+        if (cusk_run_skeleton_het(e, scr.C2.p, scr.Ness2.p, k, in.th_het, in.max_level_two, &st2) != CUSK_OK)
+            engine_die("Skeleton (het, stage two)", e);
+    }
+    else if (cusk_run_skeleton(e, scr.C2.p, k, in.Th, in.max_level_two, &st2) != CUSK_OK)
+        engine_die("Skeleton (stage two)", e);
     bs.ms_stage2 = ms_since(t);
     for (int l = 0; l < st2.levels_run; l++) bs.tests[1] += st2.tests[l];
     Bits G2 = fetch_adjacency(e);

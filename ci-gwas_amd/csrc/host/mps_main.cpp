@@ -3,7 +3,7 @@
 // Same positional argv contracts, stdout milestones, exit codes and output files as the
 // reference's native CLI (/root/reference/cusk/apps/mps.cpp:17-121, src/cli.cpp:194-346,
 // :432-678), so that ci-gwas.py (or this repo's cli shim) can call it unchanged:
-//   mps cusk   <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index>
+//   mps cusk   <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het]
 //   mps cuskss <mxm> <mxp> <mxp_se> <pxp> <pxp_se> <time_index> <block_index> <blockfile>
 //              <marker_indices> <alpha> <l1> <l2> <depth> <num_samples> <outdir>   ("NULL" = absent)
 // and two commands the reference does not have, for users who hold the genotypes (see SUMSTATS_USAGE):
@@ -35,7 +35,12 @@ namespace {
 const char *CUSK_USAGE = R"(
 Run the skeleton search on a single block of a block diagonal genomic covariance matrix.
 
-usage: mps cusk <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index>
+usage: mps cusk <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het]
+
+arguments:
+    het             test every marker-trait and trait-trait pair at the number of individuals it was observed on (.phen
+                    with NA entries): prefilter, both skeleton stages and the separating sets of the block; the sizes are
+                    those `cuskss-bed ... het` uses for the same pairs.  Same five output files.
 )";
 
 // wall-clock phase marks, printed as "[t] <phase>: <ms> ms" when CUSK_TIMING is set (tools/e2e_block.py)
@@ -55,24 +60,18 @@ struct PhaseTimer
 
 int cmd_cusk(int argc, char **argv)
 {
-    if (argc < 11)
+    CuskInputs in;
+    std::string outdir;
+    int block_index = 0;
+    if (!parse_cusk_args(argc, argv, in, outdir, block_index))
     {
         std::cout << CUSK_USAGE << std::endl;
         std::exit(1);
     }
-    CuskInputs in;
-    in.phen_path = argv[2];
-    in.bfiles = argv[3];
-    in.block_path = argv[4];
-    in.alpha = std::stof(argv[5]);
-    in.max_level = std::stoi(argv[6]);
-    in.max_level_two = std::stoi(argv[7]);
-    in.depth = std::stoi(argv[8]);
-    const std::string outdir = argv[9];
-    const int block_index = std::stoi(argv[10]);
     std::cout << "Got args: \n.phen: " << in.phen_path << "\nbfiles: " << in.bfiles << "\n.blocks: " << in.block_path
               << "\nalpha: " << in.alpha << "\nmax_level: " << in.max_level << "\nmax_level_two: " << in.max_level_two
               << "\ndepth: " << in.depth << "\noutdir: " << outdir << "\nblock-index: " << block_index << std::endl;
+    if (in.het) std::cout << "het: per-pair sample sizes" << std::endl;
 
     PhaseTimer tm;
     check_path(outdir);
@@ -82,6 +81,7 @@ int cmd_cusk(int argc, char **argv)
     std::cout << "Number of levels: " << in.max_level << std::endl;
     std::cout << "Setting level thr for cuPC: " << std::endl;
     for (int i = 0; i <= std::min(in.max_level, ML); ++i) std::cout << "\t Level: " << i << " thr: " << in.Th[i] << std::endl;
+    if (in.het) std::cout << "het: every test at quantile " << in.th_het << " / sqrt(mean pair size - level - 3) instead" << std::endl;
     if (std::getenv("CUSK_WRITE_FULL_CORRMATS")) in.full_corrmats_dir = outdir;
 
     cusk_engine *e = nullptr;
@@ -97,6 +97,9 @@ int cmd_cusk(int argc, char **argv)
     {
         std::cout << "[t] inputs (bed slice, means, stds): " << bs.ms_inputs << " ms\n[t] correlation build (H2D + kernels + mxp D2H): "
                   << bs.ms_corr << " ms" << std::endl;
+        if (in.het)
+            std::cout << "[t] of which pair counts: " << bs.ms_counts << " ms\n[t] of which size chain + sample-size matrix: " << bs.ms_ess
+                      << " ms" << std::endl;
         if (kept)
         {
             std::cout << "[t] skeleton stage one: " << bs.ms_stage1 << " ms\n[t] adjacency fetch + prune + sub-matrix gather: "

@@ -3,8 +3,9 @@
 //
 // sweep_kernel is the complete level-l kernel (cuPC-S.cu cal_Indepl1..14,
 // hetcor-cuPC-S.cu cal_Indepl1_ess..14_ess): it is what runs when the fast filter is switched
-// off, for level 1 on asymmetric / heterogeneous-ESS inputs, and as the fallback when the
-// recheck queue overflows.  recheck_kernel evaluates the tests the fast filter could not
+// off, for level 1 on asymmetric / heterogeneous-ESS inputs, as the fallback when the
+// recheck queue overflows, and at every level of cusk_run_skeleton_het (MODE 0 with HET:
+// Skeleton's selection state, hetcor's per-test threshold).  recheck_kernel evaluates the tests the fast filter could not
 // certify; finalize_kernel turns the selected ranks into sparse separating-set records.
 #include <algorithm>
 
@@ -126,7 +127,9 @@ hipError_t launch_sweep_exact(int mode, bool het, int L, const SweepParams &p, i
     {
 #define CUSK_CASE(LL)                                                               \
     case LL:                                                                        \
-        if (mode == 0) return launch_exact_L<LL, 0, false>(p, cls, st);             \
+        if (mode == 0)                                                              \
+            return het ? launch_exact_L<LL, 0, true>(p, cls, st)                    \
+                       : launch_exact_L<LL, 0, false>(p, cls, st);                  \
         return het ? launch_exact_L<LL, 1, true>(p, cls, st)                        \
                    : launch_exact_L<LL, 1, false>(p, cls, st);
         CUSK_FOR_LEVELS(CUSK_CASE)

@@ -71,6 +71,12 @@ class BlockSet:
             lib().cusk_blockset_close(self.h)
             self.h = None
 
+    def set_het(self, het: bool = True) -> None:
+        """cusk_blockset_set_het: run_block takes the per-pair sample-size branch (`mps cusk ... het`); run_batch then fails"""
+        if lib().cusk_blockset_set_het(self.h, 1 if het else 0) != 0:
+            raise RuntimeError("cusk_blockset_set_het failed")
+        self.het = bool(het)
+
     def markers(self, i: int) -> int:
         return int(lib().cusk_blockset_block_markers(self.h, i))
 
@@ -563,7 +569,8 @@ def run_job(bs, outdir: str | None, device: int, inflight: int = 1, schedule: st
     return allr, stats, (owned if owned is not None else sorted(stats))
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    """The command line of this driver; batch_vars comes back resolved (0 = one block per engine run)."""
     ap = argparse.ArgumentParser(prog="run_blocks", description="cusk on every LD block of a .blocks file, sharded over the GPUs of one node")
     ap.add_argument("phen")
     ap.add_argument("bfiles")
@@ -580,12 +587,24 @@ def main(argv=None):
                     help="merge (batched execution): every rank writes the files of its own blocks, the merged skeleton is gathered "
                          "to rank 0 (RCCL) and written there as merged_blocks*; rank0: full results gathered to rank 0, which writes "
                          "every file; local: every rank writes its own blocks' files, no exchange")
-    ap.add_argument("--batch-vars", type=int, default=16384,
+    ap.add_argument("--batch-vars", type=int, default=None,
                     help="blocks are run in batches of at most this many (padded) variables, one level loop per stage for the "
-                         "whole batch; 0: one block per engine run")
+                         "whole batch (default 16384); 0: one block per engine run")
+    ap.add_argument("--het", action="store_true",
+                    help="every block at per-pair sample sizes (`mps cusk ... het`: phenotypes with NA entries); runs one "
+                         "block per engine run (--batch-vars 0), the batched run has no such form")
     ap.add_argument("--no-stage", action="store_true", help="do not keep the whole .bed in HBM; every block uploads its slice")
     ap.add_argument("--device", type=int, default=None, help="GPU of this rank (default LOCAL_RANK modulo the device count)")
     args = ap.parse_args(argv)
+    if args.het and args.batch_vars not in (None, 0):
+        ap.error("--het runs one block per engine run: it cannot be combined with a non-zero --batch-vars")
+    if args.batch_vars is None:
+        args.batch_vars = 0 if args.het else 16384
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -608,6 +627,8 @@ def main(argv=None):
         sys.exit(f"file or directory not found: {args.outdir}")
     t0 = time.perf_counter()
     bs = BlockSet(args.phen, args.bfiles, args.blocks, args.alpha, args.max_level, args.max_level_two, args.depth)
+    if args.het:
+        bs.set_het(True)
     t_open = time.perf_counter() - t0
     # no per-level HIP events: nothing here reads the per-level kernel times, and every event costs the launch-bound
     # small blocks a few microseconds of device time

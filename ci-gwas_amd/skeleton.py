@@ -304,6 +304,22 @@ class Engine:
                                           float(np.float32(th)), int(maxlevel), _ptr(ti), C.byref(st)))
         return Stats.of(st)
 
+    def run_skeleton_het(self, C_dev: int, N_dev: int, n: int, th: float, maxlevel: int) -> Stats:
+        """cusk_run_skeleton_het: Skeleton's outputs (adjacency, separating sets, pMax) with every test decided at the
+        per-pair sample sizes N_dev (n x n float32 on the device, e.g. from `ess_square`); th = hetcor_threshold(alpha)"""
+        st = CuskStats()
+        self._check(lib().cusk_run_skeleton_het(self.h, C_dev, N_dev, int(n), float(np.float32(th)), int(maxlevel), C.byref(st)))
+        return Stats.of(st)
+
+    def ess_square(self, mxp_ess, pxp_ess, m: int, p: int, n_uniform: float, N_dev: int) -> None:
+        """cusk_ess_square: the (m + p)^2 float32 sample-size matrix at the device address N_dev (any float boundary):
+        n_uniform between markers, mxp_ess (m x p) mirrored, pxp_ess (p x p) with NaN on its diagonal"""
+        mxp_ess = np.ascontiguousarray(mxp_ess, np.float32).reshape(-1) if int(m) * int(p) else None
+        pxp_ess = np.ascontiguousarray(pxp_ess, np.float32).reshape(-1) if int(p) else None
+        if (mxp_ess is not None and mxp_ess.size != int(m) * int(p)) or (pxp_ess is not None and pxp_ess.size != int(p) * int(p)):
+            raise ValueError("ess_square: mxp_ess must hold m * p values and pxp_ess p * p")
+        self._check(lib().cusk_ess_square(self.h, _ptr(mxp_ess), _ptr(pxp_ess), int(m), int(p), float(np.float32(n_uniform)), N_dev))
+
     def adjacency(self) -> np.ndarray:
         n = lib().cusk_result_n(self.h)
         G = np.zeros((n, n), np.int32)

@@ -176,6 +176,21 @@ int cusk_run_hetcor(cusk_engine *e, const float *C_dev, const float *N_dev, floa
                     const int *G_init_dev, int n, float th, int maxlevel, const int *time_index,
                     cusk_stats *stats);
 
+/* `Skeleton` semantics at per-pair sample sizes: the outputs of cusk_run_skeleton (lowest passing conditioning set per
+ * ordered pair in Skeleton's enumeration -- neighbours ascending, combinations lexicographic --, separating-set records,
+ * pMax; read through cusk_result_adj_*, cusk_result_sepsets, cusk_result_sepset_dense, cusk_result_pmax) with every test
+ * decided at the threshold of cusk_run_hetcor.  N_dev: the n*n fp32 sample-size matrix as cusk_run_hetcor takes it (e.g.
+ * from cusk_ess_square); th = cusk_hetcor_threshold(alpha).  Level 0 removes the pair (i, j) when its Fisher z lies below
+ * th / sqrt(N[i,j] - 3) and records the empty set and that z; a test of X, Y given S, |S| = l >= 1, compares with
+ * th / sqrt(mean - l - 3), mean = the float sum of the (l + 2)(l + 1) / 2 sizes among {X, Y} + S, each truncated to int,
+ * divided by their number (mean_ess, hetcor-cuPC-S.cu:3068-3088).  A NaN or negative radicand gives a NaN threshold: the
+ * comparison is false and the edge stays.  There is no time index and no starting graph.  With every size equal to N the
+ * result is that of cusk_run_skeleton with Th[l] = th / sqrt(N - l - 3) formed in that arithmetic.
+ * Every level runs on the exact path.  Not supported, each an error with a message in cusk_last_error: an engine that is
+ * row-sharded (cusk_engine_set_row_shard with world > 1), option "validate"; there is no batched form. */
+int cusk_run_skeleton_het(cusk_engine *e, const float *C_dev, const float *N_dev, int n, float th, int maxlevel,
+                          cusk_stats *stats);
+
 /* Batched Skeleton run: `nblk` independent blocks (the LD blocks of one GPU's share of a chromosome job, or their reduced
  * stage-two sets) swept in ONE run.  The reference has no counterpart: it runs one block per process (src/cli.cpp:507-512,
  * README.md:62); per block the result is that of cusk_run_skeleton on the block alone (adjacency, separating sets).
@@ -307,6 +322,14 @@ int cusk_sumstats_write(const char *outdir, const float *mxm_tri, size_t k, cons
  * counts are there. */
 int cusk_pair_counts(cusk_engine *e, const unsigned char *bed, const float *phen, const int *marker_ix, size_t k,
                      size_t m_total, size_t N, size_t p, int *mxp_n_host, int *pxp_n_host);
+/* The square sample-size matrix of a block of m markers and p traits, written on the device: N_dev (n x n float32, n =
+ * m + p, row-major, a device pointer that may start at any float) receives n_uniform between two markers,
+ * mxp_ess[i * p + t] at (i, m + t) and (m + t, i), pxp_ess[a * p + b] at (m + a, m + b) for a != b and NaN on the trait
+ * diagonal -- what make_square_cuskss_inputs (cli.cpp:89-173) assembles on the host for `cuskss`.  mxp_ess (m x p) and
+ * pxp_ess (p x p) are host arrays (device-resident ones are read in place); either may be NULL when it is empty.
+ * Returns when the matrix is written. */
+int cusk_ess_square(cusk_engine *e, const float *mxp_ess, const float *pxp_ess, size_t m, size_t p, float n_uniform,
+                    float *N_dev);
 /* Host only.  The sample size the mxp / pxp loaders of `cuskss` make of a correlation and its standard error:
  * ((1 - r^2) / se)^2 with their float / double mix (marker_trait_summary_stats.cpp:161-164). */
 float cusk_ess_from_se(float r, float se);
@@ -437,6 +460,11 @@ int cusk_blockset_run_block(cusk_blockset *bs, cusk_engine *e, int block_index, 
 int cusk_blockset_run_block_next(cusk_blockset *bs, cusk_engine *e, int block_index, int next_index,
                                  cusk_block_result **out, cusk_block_stats *stats);
 const char *cusk_blockset_last_error(void);
+/* het = 1: cusk_blockset_run_block / _run_block_next run every block at per-pair sample sizes (`mps cusk ... het`: counts of
+ * complete observations from the genotypes and the .phen, cusk_run_skeleton_het for both stages, the prefilter at the
+ * marker x trait sizes); cusk_blockset_run_batch then returns an error (the batched run has no such form).  Set it
+ * before running blocks; not while other threads run blocks of the set. */
+int cusk_blockset_set_het(cusk_blockset *bs, int het);
 /* Forgets what the block set keeps for engine e -- its device scratch (block matrices) and the state of a correlation
  * build started ahead -- and releases that memory.  Call before destroying an engine that ran blocks of this set when the
  * set outlives it (cusk_blockset_close releases everything anyway). */

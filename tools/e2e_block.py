@@ -1,5 +1,5 @@
 """Wall-clock of `mps cusk` on one synthetic 10k-SNP block, end to end (files in, files out), with a phase breakdown
-(the host program prints its own timings with CUSK_TIMING=1)."""
+(the host program prints its own timings with CUSK_TIMING=1).  HET=1 appends `het`, L2 sets max-level-two."""
 import os, subprocess, sys, tempfile, time
 import numpy as np
 sys.path.insert(0, ".")
@@ -20,7 +20,8 @@ out = os.path.join(d, "out"); os.makedirs(out)
 env = dict(os.environ, CUSK_TIMING="1")
 for rep in range(1):
     t0 = time.perf_counter()
-    r = subprocess.run([MPS_PATH, "cusk", os.path.join(d, "blk.phen"), stem, os.path.join(d, "blk.blocks"), "0.0001", "5", "14", "1", out, "0"],
+    r = subprocess.run([MPS_PATH, "cusk", os.path.join(d, "blk.phen"), stem, os.path.join(d, "blk.blocks"), "0.0001", "5", os.environ.get("L2", "14"), "1", out, "0"]
+                       + (["het"] if os.environ.get("HET") else []),  # HET=1: per-pair sample sizes (`mps cusk ... het`)
                        capture_output=True, text=True, env=env)
     dt = time.perf_counter() - t0
     print(f"run {rep}: rc={r.returncode} wall {dt:.3f} s")
