@@ -96,6 +96,7 @@ SYMBOLS = {
     "cusk_run_hetcor": (_i, [_vp, _vp, _vp, _f, _vp, _i, _f, _i, _vp, C.POINTER(CuskStats)]),
     "cusk_run_skeleton_het": (_i, [_vp, _vp, _vp, _i, _f, _i, C.POINTER(CuskStats)]),
     "cusk_run_skeleton_batch": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, C.POINTER(CuskStats)]),
+    "cusk_run_skeleton_batch_het": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _f, _i, C.POINTER(CuskStats)]),
     "cusk_result_adj_bits_blocks": (_i, [_vp, _vp]),
     "cusk_result_adj_bits_blocks_tail": (_i, [_vp, _i, _vp]),
     "cusk_result_adj_rows": (_i, [_vp, _i, _i, _vp]),
@@ -121,6 +122,7 @@ SYMBOLS = {
     "cusk_sumstats_write": (_i, [C.c_char_p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, C.c_char_p, _sz]),
     "cusk_pair_counts": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),
     "cusk_ess_square": (_i, [_vp, _vp, _vp, _sz, _sz, _f, _vp]),
+    "cusk_ess_square_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _sz, _f, _i, _vp]),
     "cusk_ess_from_se": (_f, [_f, _f]),
     "cusk_se_from_count": (_f, [_f, _i]),
     "cusk_sumstats_write_se": (_i, [C.c_char_p, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, C.c_char_p, _sz]),
@@ -145,6 +147,7 @@ SYMBOLS = {
     "cusk_blockset_set_het": (_i, [_vp, _i]),
     "cusk_blockset_release_engine": (None, [_vp, _vp]),
     "cusk_blockset_run_batch": (_i, [_vp, _vp, _vp, _i, C.POINTER(_vp), _vp]),
+    "cusk_blockset_run_batch_het": (_i, [_vp, _vp, _vp, _i, C.POINTER(_vp), _vp]),
     "cusk_batch_result_count": (_i, [_vp]),
     "cusk_batch_result_block_index": (_i, [_vp, _i]),
     "cusk_batch_result_block": (_vp, [_vp, _i]),

@@ -185,8 +185,8 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
         float th0 = a.Th[0];
         if (a.mode == 1 && !het) th0 = (float)((double)a.Th[0] / std::sqrt((double)a.ess_uniform - 3.0));
         if (a.row_range)
-            CUSK_HIP(e, launch_level0_batch(a.C, e->adj.as<unsigned long long>(), e->adj0.as<unsigned long long>(), e->deg.as<int>(), n,
-                                            words, a.row_range, th0, s));
+            CUSK_HIP(e, launch_level0_batch(a.C, het0 ? a.Ness : nullptr, e->adj.as<unsigned long long>(), e->adj0.as<unsigned long long>(),
+                                            e->deg.as<int>(), n, words, a.row_range, th0, s));
         else
         {
             CUSK_HIP(e, launch_level0(a.C, het ? a.Ness : nullptr, a.Ginit, e->adj.as<unsigned long long>(), n, words, th0,
@@ -1038,21 +1038,16 @@ extern "C" int cusk_run_skeleton(cusk_engine *e, const float *C_dev, int n, cons
     return run_levels(e, a, stats);
 }
 
-// Batched Skeleton run: `nblk` independent blocks laid out along the diagonal of one n x n allocation (include/cusk_hip.h).
-// One plan / fill / sweep / finalise chain per level serves every block: after level 0 the engine only works on CSR rows,
-// and a row never meets a column outside its block, so nothing but level 0 and the level-1 row staging knows about blocks.
-extern "C" int cusk_run_skeleton_batch(cusk_engine *e, const float *C_dev, int n, int nblk, const int *lo, const int *hi,
-                                       const float *Th, int maxlevel, cusk_stats *stats)
+// the tables of a batched run (checked layout, per-row column range and block number, packed-bitmap offsets: uploaded on the
+// engine's stream) and the RunArgs fields that describe the blocks; shared by the batched entry points
+static int batch_setup(cusk_engine *e, const char *who, int n, int nblk, const int *lo, const int *hi, RunArgs &a)
 {
-    if (!e) return CUSK_ERR_ARG;
-    if (!C_dev || !lo || !hi || !Th || n <= 0 || nblk <= 0) return fail(e, CUSK_ERR_ARG, "bad arguments");
-    if (e->shard_world > 1) return fail(e, CUSK_ERR_ARG, "batched runs are not row-sharded");
     int prev = 0, span = 0;
     long long pairs0 = 0;
     for (int b = 0; b < nblk; b++)
     {
         if ((lo[b] & 63) != 0 || lo[b] < prev || hi[b] < lo[b] || hi[b] > n)
-            return fail(e, CUSK_ERR_ARG, "cusk_run_skeleton_batch: block bases must be ascending multiples of 64 inside the matrix");
+            return fail(e, CUSK_ERR_ARG, std::string(who) + ": block bases must be ascending multiples of 64 inside the matrix");
         prev = hi[b];
         span = std::max(span, hi[b] - lo[b]);
         pairs0 += (long long)(hi[b] - lo[b]) * (hi[b] - lo[b] - 1) / 2;
@@ -1098,16 +1093,59 @@ extern "C" int cusk_run_skeleton_batch(cusk_engine *e, const float *C_dev, int n
     CUSK_HIP(e, hipMemcpyAsync(e->blk_woff.p, wo, bytes_wo, hipMemcpyHostToDevice, e->stream));
     e->batch_lo.assign(lo, lo + nblk);
     e->batch_hi.assign(hi, hi + nblk);
+    a.row_range = e->row_range.as<int2>();
+    a.max_span = span;
+    a.level0_pairs = pairs0;
+    return CUSK_OK;
+}
+
+// Batched Skeleton run: `nblk` independent blocks laid out along the diagonal of one n x n allocation (include/cusk_hip.h).
+// One plan / fill / sweep / finalise chain per level serves every block: after level 0 the engine only works on CSR rows,
+// and a row never meets a column outside its block, so nothing but level 0 and the level-1 row staging knows about blocks.
+extern "C" int cusk_run_skeleton_batch(cusk_engine *e, const float *C_dev, int n, int nblk, const int *lo, const int *hi,
+                                       const float *Th, int maxlevel, cusk_stats *stats)
+{
+    if (!e) return CUSK_ERR_ARG;
+    if (!C_dev || !lo || !hi || !Th || n <= 0 || nblk <= 0) return fail(e, CUSK_ERR_ARG, "bad arguments");
+    if (e->shard_world > 1) return fail(e, CUSK_ERR_ARG, "batched runs are not row-sharded");
     RunArgs a{};
     a.mode = 0;
     a.C = C_dev;
     a.Th = Th;
     a.n = n;
     a.maxlevel = maxlevel;
-    a.row_range = e->row_range.as<int2>();
-    a.max_span = span;
-    a.level0_pairs = pairs0;
-    const int rc = run_levels(e, a, stats);
+    int rc = batch_setup(e, "cusk_run_skeleton_batch", n, nblk, lo, hi, a);
+    if (rc != CUSK_OK) return rc;
+    rc = run_levels(e, a, stats);
+    if (rc != CUSK_OK) e->batch_lo.clear();
+    return rc;
+}
+
+// The batched run at per-pair sample sizes: the het0 plan of run_levels (exact path only: no filter, no vectorised or
+// union-major sweep, no level-1 row / pair kernels) with row_range set -- level 0 by level0_batch_kernel<true>, which
+// also writes the level-0 copy and the degrees; from level 1 on the engine works on CSR rows, and the exact sweep reads
+// C[a * n + b] and N[a * n + b] at the stride of the allocation, inside the row's own block only.
+extern "C" int cusk_run_skeleton_batch_het(cusk_engine *e, const float *C_dev, const float *N_dev, int n, int nblk, const int *lo,
+                                           const int *hi, float th, int maxlevel, cusk_stats *stats)
+{
+    if (!e) return CUSK_ERR_ARG;
+    if (!C_dev || !lo || !hi || n <= 0 || nblk <= 0) return fail(e, CUSK_ERR_ARG, "bad arguments");
+    if (!N_dev) return fail(e, CUSK_ERR_ARG, "cusk_run_skeleton_batch_het: needs the sample-size matrix");
+    if (e->shard_world > 1)
+        return fail(e, CUSK_ERR_ARG, "cusk_run_skeleton_batch_het: a row-sharded engine is not supported (per-pair sample sizes run on one engine)");
+    if (e->opt_validate)
+        return fail(e, CUSK_ERR_ARG, "cusk_run_skeleton_batch_het: option validate is not supported (every test already runs on the exact path)");
+    RunArgs a{};
+    a.mode = 0;
+    a.C = C_dev;
+    a.Ness = N_dev;
+    float thv[1] = {th};
+    a.Th = thv;
+    a.n = n;
+    a.maxlevel = maxlevel;
+    int rc = batch_setup(e, "cusk_run_skeleton_batch_het", n, nblk, lo, hi, a);
+    if (rc != CUSK_OK) return rc;
+    rc = run_levels(e, a, stats);
     if (rc != CUSK_OK) e->batch_lo.clear();
     return rc;
 }

@@ -21,6 +21,7 @@ namespace host {
 struct BatchScratch
 {
     DevMat C, C2;
+    DevMat Ness, Ness2;  // batches at per-pair sample sizes: the size matrices of both stages, laid out like C and C2
 };
 
 struct BatchStats
@@ -44,6 +45,31 @@ struct BatchBlockOut
 
 inline int pad64(size_t v) { return (int)((v + 63) / 64 * 64); }
 
+// The count pass of a batch at per-pair sample sizes: cusk_pair_counts takes ONE ascending, distinct list of marker rows,
+// a batch names its blocks in any order.  ix = the markers of all blocks in ascending order of the blocks' first marker;
+// row0[b] = where block b's (blocks[b] of the caller: first[b], m[b] markers) rows start in that list.  False when two
+// blocks share a marker (the same block named twice): no such list exists, the caller counts block by block.
+inline bool plan_count_pass(const std::vector<long long> &first, const std::vector<int> &m, std::vector<int> &ix,
+                            std::vector<size_t> &row0)
+{
+    const size_t B = first.size();
+    std::vector<size_t> order(B);
+    std::iota(order.begin(), order.end(), (size_t)0);
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return first[a] < first[b]; });
+    ix.clear();
+    row0.assign(B, 0);
+    long long end = 0;
+    for (size_t b : order)
+    {
+        if (m[b] <= 0) continue;
+        if (first[b] < end) return false;
+        row0[b] = ix.size();
+        for (int i = 0; i < m[b]; i++) ix.push_back((int)(first[b] + i));
+        end = first[b] + m[b];
+    }
+    return true;
+}
+
 // rows lo..hi-1 of one block out of the packed bitmap of cusk_result_adj_bits_blocks
 inline Bits block_bits(const std::vector<uint64_t> &packed, size_t &pos, int k)
 {
@@ -56,8 +82,11 @@ inline Bits block_bits(const std::vector<uint64_t> &packed, size_t &pos, int k)
 }
 
 // cli.cpp:521-677 for every block of `blocks` on the engine's device.  outs[i] belongs to blocks[i].
+// het: every block as run_cusk_block runs it on a set at per-pair sample sizes (`mps cusk ... het`) -- counts of complete
+// observations for the batch's markers in one pass, the sizes of every block through block_sample_sizes, the het
+// prefilter, both stages through cusk_run_skeleton_batch_het with the sizes on the diagonal of a second allocation.
 inline void run_cusk_batch(cusk_engine *e, const CuskInputs &in, const StagedInputs &staged, const std::vector<int> &blocks,
-                           BatchScratch &scr, std::vector<BatchBlockOut> &outs, BatchStats &bs)
+                           BatchScratch &scr, std::vector<BatchBlockOut> &outs, BatchStats &bs, bool het = false)
 {
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point &t) {
@@ -116,6 +145,74 @@ inline void run_cusk_batch(cusk_engine *e, const CuskInputs &in, const StagedInp
                               scr.C.p, mxp.data()) != CUSK_OK)
         engine_die("correlation build", e);
     mark("mxp");
+    het = het && p > 0;  // (without traits there is no pair with a size of its own; run_cusk_block takes the plain branch too)
+    std::vector<float> mxp_ess, pxp_ess;  // het: the blocks' m x p tables back to back, one p x p table per block
+    if (het)
+    {
+        // counts: one pass over the batch's markers (sorted for the call, mapped back to the order of the batch); block by
+        // block when the batch names a block twice
+        std::vector<int> mxp_n(msum * p), pxp_n(p * p), ix;
+        std::vector<size_t> row0;
+        if (plan_count_pass(first, m, ix, row0))
+        {
+            std::vector<int> sorted_n(msum * p);
+            if (cusk_pair_counts(e, staged.bed, staged.phen, ix.data(), ix.size(), (in.bed.size - 3) / bpc, N, p, sorted_n.data(),
+                                 pxp_n.data()) != CUSK_OK)
+                engine_die("pair counts (batch)", e);
+            size_t o = 0;
+            for (int b = 0; b < B; b++)
+            {
+                const size_t cnt = (size_t)m[(size_t)b] * p;
+                std::copy_n(sorted_n.begin() + (long)(row0[(size_t)b] * p), cnt, mxp_n.begin() + (long)o);
+                o += cnt;
+            }
+        }
+        else
+        {
+            size_t o = 0;
+            for (int b = 0; b < B; b++)
+            {
+                const size_t mb = (size_t)m[(size_t)b];
+                if (cusk_pair_counts(e, staged.bed + (size_t)first[(size_t)b] * bpc, staged.phen, nullptr, mb, mb, N, p, mxp_n.data() + o,
+                                     pxp_n.data()) != CUSK_OK)
+                    engine_die("pair counts (batch)", e);
+                o += mb * p;
+            }
+        }
+        mark("counts");
+        // sizes: per block the chain of block_sample_sizes, the trait x trait correlations from the block's own diagonal
+        // block (waits for the marker x marker part of the build, which writes them)
+        std::vector<float> pxp((size_t)B * p * p);
+        {
+            const size_t rows = (size_t)B * p;
+            std::vector<int> idx(rows), row_k(rows, (int)p);
+            std::vector<long long> row_first(rows), row_out(rows);
+            for (int b = 0; b < B; b++)
+                for (size_t t = 0; t < p; t++)
+                {
+                    const size_t r = (size_t)b * p + t;
+                    idx[r] = base[(size_t)b] + m[(size_t)b] + (int)t;
+                    row_first[r] = (long long)((size_t)b * p);
+                    row_out[r] = (long long)(r * p);
+                }
+            if (cusk_gather_rows(e, scr.C.p, (int)n1, idx.data(), (long long)rows, idx.data(), row_k.data(), row_first.data(),
+                                 row_out.data(), (long long)rows, pxp.data(), (long long)pxp.size(), 0) != CUSK_OK)
+                engine_die("gather (trait correlations, batch)", e);
+        }
+        mxp_ess.resize(msum * p);
+        pxp_ess.resize((size_t)B * p * p);
+        std::vector<float> me, pe;
+        size_t o = 0;
+        for (int b = 0; b < B; b++)
+        {
+            const size_t mb = (size_t)m[(size_t)b];
+            block_sample_sizes(mxp.data() + o, mxp_n.data() + o, pxp.data() + (size_t)b * p * p, pxp_n.data(), mb, p, me, pe);
+            std::copy(me.begin(), me.end(), mxp_ess.begin() + (long)o);
+            std::copy(pe.begin(), pe.end(), pxp_ess.begin() + (long)((size_t)b * p * p));
+            o += mb * p;
+        }
+        mark("sizes");
+    }
     std::vector<unsigned char> keep((size_t)B, 0);
     std::vector<int> kept;
     {
@@ -123,7 +220,8 @@ inline void run_cusk_batch(cusk_engine *e, const CuskInputs &in, const StagedInp
         for (int b = 0; b < B; b++)
         {
             const size_t cnt = (size_t)m[(size_t)b] * p;
-            const int num_sig = count_significant(mxp.data() + o, cnt, in.Th[0]);
+            const int num_sig = het ? count_significant_het(mxp.data() + o, mxp_ess.data() + o, cnt, in.th_het)
+                                    : count_significant(mxp.data() + o, cnt, in.Th[0]);
             o += cnt;
             outs[(size_t)b].num_sig = num_sig;
             outs[(size_t)b].skipped = (num_sig == 0);
@@ -137,6 +235,10 @@ inline void run_cusk_batch(cusk_engine *e, const CuskInputs &in, const StagedInp
     mark("prefilter");
     if (kept.empty())
     {
+        // the marker x marker part of the build is still enqueued and reads the engine's pinned table staging, which the
+        // next batch overwrites: nothing may be in flight when this returns
+        float one;
+        if (cusk_engine_download(e, &one, scr.C.p, sizeof(one)) != CUSK_OK) engine_die("correlation build (batch)", e);
         bs.ms_corr = ms_since(t);
         return;
     }
@@ -151,7 +253,35 @@ inline void run_cusk_batch(cusk_engine *e, const CuskInputs &in, const StagedInp
         lo1[(size_t)k] = base[(size_t)kept[(size_t)k]];
         hi1[(size_t)k] = lo1[(size_t)k] + m[(size_t)kept[(size_t)k]] + (int)p;
     }
-    if (cusk_run_skeleton_batch(e, scr.C.p, (int)n1, K, lo1.data(), hi1.data(), in.Th, in.max_level, &bs.stage[0]) != CUSK_OK)
+    if (het)
+    {
+        // the kept blocks' sizes onto the diagonal of an allocation shaped like C (tables of the kept blocks, back to back)
+        std::vector<int> mk((size_t)K);
+        std::vector<float> me, pe((size_t)K * p * p);
+        size_t cnt_m = 0;
+        for (int k = 0; k < K; k++) cnt_m += (size_t)m[(size_t)kept[(size_t)k]] * p;
+        me.reserve(cnt_m);
+        {
+            std::vector<size_t> off((size_t)B + 1, 0);
+            for (int b = 0; b < B; b++) off[(size_t)b + 1] = off[(size_t)b] + (size_t)m[(size_t)b] * p;
+            for (int k = 0; k < K; k++)
+            {
+                const size_t b = (size_t)kept[(size_t)k];
+                mk[(size_t)k] = m[b];
+                me.insert(me.end(), mxp_ess.begin() + (long)off[b], mxp_ess.begin() + (long)off[b + 1]);
+                std::copy_n(pxp_ess.begin() + (long)(b * p * p), p * p, pe.begin() + (long)((size_t)k * p * p));
+            }
+        }
+        scr.Ness.reserve(n1 * n1);
+        if (cusk_ess_square_batch(e, me.data(), pe.data(), K, mk.data(), lo1.data(), p, (float)N, (int)n1, scr.Ness.p) != CUSK_OK)
+            engine_die("sample-size matrix (batch)", e);
+        mark("ess_square");
+        bs.ms_corr += ms_since(t);
+        if (cusk_run_skeleton_batch_het(e, scr.C.p, scr.Ness.p, (int)n1, K, lo1.data(), hi1.data(), in.th_het, in.max_level, &bs.stage[0]) !=
+            CUSK_OK)
+            engine_die("Skeleton (het, batch)", e);
+    }
+    else if (cusk_run_skeleton_batch(e, scr.C.p, (int)n1, K, lo1.data(), hi1.data(), in.Th, in.max_level, &bs.stage[0]) != CUSK_OK)
         engine_die("Skeleton (batch)", e);
     mark("stage1");
     for (int l = 0; l < bs.stage[0].levels_run; l++)
@@ -224,12 +354,25 @@ inline void run_cusk_batch(cusk_engine *e, const CuskInputs &in, const StagedInp
         if (cusk_gather_rows(e, scr.C.p, (int)n1, idx.data(), (long long)rows2, row_src.data(), row_k.data(), row_first.data(),
                              row_out.data(), (long long)rows2, scr.C2.p, 0, 1) != CUSK_OK)
             engine_die("gather (batch)", e);
+        if (het)
+        {  // the sizes of the retained variables, by the very index tables
+            scr.Ness2.reserve(n2 * n2);
+            if (cusk_gather_rows(e, scr.Ness.p, (int)n1, idx.data(), (long long)rows2, row_src.data(), row_k.data(), row_first.data(),
+                                 row_out.data(), (long long)rows2, scr.Ness2.p, 0, 1) != CUSK_OK)
+                engine_die("gather (sizes, batch)", e);
+        }
     }
     mark("gather2");
     bs.ms_prune = ms_since(t);
 
     // ---- stage two: Skeleton again on every reduced set, each from its complete graph ----
-    if (cusk_run_skeleton_batch(e, scr.C2.p, (int)n2, K, lo2.data(), hi2.data(), in.Th, in.max_level_two, &bs.stage[1]) != CUSK_OK)
+    if (het)
+    {
+        if (cusk_run_skeleton_batch_het(e, scr.C2.p, scr.Ness2.p, (int)n2, K, lo2.data(), hi2.data(), in.th_het, in.max_level_two,
+                                        &bs.stage[1]) != CUSK_OK)
+            engine_die("Skeleton (het, stage two, batch)", e);
+    }
+    else if (cusk_run_skeleton_batch(e, scr.C2.p, (int)n2, K, lo2.data(), hi2.data(), in.Th, in.max_level_two, &bs.stage[1]) != CUSK_OK)
         engine_die("Skeleton (stage two, batch)", e);
     mark("stage2");
     for (int l = 0; l < bs.stage[1].levels_run; l++)

@@ -227,18 +227,10 @@ struct cusk_batch_result
     std::vector<int> index;
 };
 
-extern "C" int cusk_blockset_run_batch(cusk_blockset *bs, cusk_engine *e, const int *block_indices, int nblocks,
-                                       cusk_batch_result **out, cusk_batch_stats *stats)
+// het: every block at per-pair sample sizes (run_cusk_batch's het branch), whatever the block set's own switch says
+static int run_batch(cusk_blockset *bs, cusk_engine *e, const int *block_indices, int nblocks, cusk_batch_result **out,
+                     cusk_batch_stats *stats, bool het)
 {
-    if (!bs || !e || !out || !block_indices || nblocks < 0) return CUSK_ERR_ARG;
-    *out = nullptr;
-    if (bs->in.het)
-    {
-        copy_err("cusk_blockset_run_batch: this block set runs at per-pair sample sizes (cusk_blockset_set_het), which the "
-                 "batched run does not support; run its blocks with cusk_blockset_run_block",
-                 nullptr, 0);
-        return CUSK_ERR_ARG;
-    }
     if (!bs->staged_of(e) && cusk_blockset_stage(bs, e) != CUSK_OK) return CUSK_ERR_HIP;
     const StagedInputs *staged = bs->staged_of(e);
     BatchScratch &scratch = bs->batch_scratch_of(e);
@@ -247,7 +239,7 @@ extern "C" int cusk_blockset_run_batch(cusk_blockset *bs, cusk_engine *e, const 
     {
         std::vector<BatchBlockOut> outs;
         BatchStats st;
-        run_cusk_batch(e, bs->in, *staged, std::vector<int>(block_indices, block_indices + nblocks), scratch, outs, st);
+        run_cusk_batch(e, bs->in, *staged, std::vector<int>(block_indices, block_indices + nblocks), scratch, outs, st, het);
         for (BatchBlockOut &o : outs)
         {
             if (o.skipped) continue;
@@ -289,6 +281,29 @@ extern "C" int cusk_blockset_run_batch(cusk_blockset *bs, cusk_engine *e, const 
         return CUSK_ERR_ARG;
     }
     return CUSK_OK;
+}
+
+extern "C" int cusk_blockset_run_batch(cusk_blockset *bs, cusk_engine *e, const int *block_indices, int nblocks,
+                                       cusk_batch_result **out, cusk_batch_stats *stats)
+{
+    if (!bs || !e || !out || !block_indices || nblocks < 0) return CUSK_ERR_ARG;
+    *out = nullptr;
+    if (bs->in.het)
+    {
+        copy_err("cusk_blockset_run_batch: this block set runs at per-pair sample sizes (cusk_blockset_set_het), which the "
+                 "batched run does not support; run its blocks with cusk_blockset_run_block",
+                 nullptr, 0);
+        return CUSK_ERR_ARG;
+    }
+    return run_batch(bs, e, block_indices, nblocks, out, stats, false);
+}
+
+extern "C" int cusk_blockset_run_batch_het(cusk_blockset *bs, cusk_engine *e, const int *block_indices, int nblocks,
+                                           cusk_batch_result **out, cusk_batch_stats *stats)
+{
+    if (!bs || !e || !out || !block_indices || nblocks < 0) return CUSK_ERR_ARG;
+    *out = nullptr;
+    return run_batch(bs, e, block_indices, nblocks, out, stats, true);
 }
 
 extern "C" int cusk_batch_result_count(const cusk_batch_result *r) { return r ? (int)r->blocks.size() : 0; }

@@ -374,15 +374,47 @@ hipError_t launch_level0(const float *C, const float *Ness, const int *Ginit, un
     return hipGetLastError();
 }
 
+// Level 0 at per-pair sample sizes: is the pair with correlation c and size nij removed at th / sqrt(nij - 3)?  A
+// single-precision estimate of z sqrt(nij - 3) settles the element unless it falls within 1e-3 of th (or the threshold is
+// too small for that band, or an operand is unusual); only then the reference's double-precision threshold and Fisher z
+// are formed.  A NaN or negative radicand gives a NaN threshold: the comparison is false, the edge stays.  These are the
+// statements of level0_kernel<true, SYM> above, one for one (that kernel is left as it is): a batch must decide every pair
+// as the block alone does, and tests/test_gpu_cusk_het_batch.py holds the two together block by block.
+__device__ __forceinline__ bool het_pair_removed(float c, float nij, float th)
+{
+    const float nm3 = nij - 3.0f;
+    const float ac = fabsf(c);
+    int fastv = 2;
+    if (nm3 > 0.0f && nm3 < 3.0e38f && ac < 1.0f && th * __frsqrt_rn(nm3) >= kThMinFilter)
+    {
+        const float sest = 0.5f * fabsf(__logf((1.0f + ac) / (1.0f - ac))) * __fsqrt_rn(nm3);
+        if (sest < th * (1.0f - 1e-3f))
+            fastv = 1;
+        else if (sest > th * (1.0f + 1e-3f))
+            fastv = 0;
+    }
+    if (fastv == 2)
+    {
+        const float lth = (float)((double)th / sqrt((double)nij - 3.0));
+        return z_below<false>(c, lth);
+    }
+    return fastv == 1;
+}
+
 // Block-diagonal level 0 (batched runs: many small LD blocks along the diagonal of one allocation, bases multiples of 64,
 // so no bitmap word straddles two blocks).  One wave per row: the words of the row's own block come from C[row, lo..hi)
 // (coalesced 256-byte pieces, ballots = bitmap words), every other word of the row is zero -- the cross-block pairs do not
 // exist.  The verdict is cal_Indepl0's (cuPC-S.cu:458-484) evaluated per ordered pair; the reference evaluates i < j and
 // mirrors, which is the same thing on a bitwise symmetric matrix (the batched correlation build and the device gather of
 // a symmetric matrix write both triangles from one value).  Writes the live bitmap, its level-0 copy and the degrees.
+// HET: the verdict of level0_kernel<true, *> at the sizes N[row, lo..hi) (same stride, same aligned 256-byte pieces); N is
+// bitwise symmetric inside the blocks like C (cusk_ess_square_batch, cusk_gather_rows), so the ordered pairs agree.  N is
+// the last argument and every het statement is compiled out of the <false> form: its code is the untemplated kernel's.
+template <bool HET>
 __global__ void __launch_bounds__(256) level0_batch_kernel(const float *__restrict__ C, unsigned long long *adj,
                                                             unsigned long long *adj0, int *deg, int n, int words,
-                                                            const int2 *__restrict__ row_range, float th, float c_lo, float c_hi)
+                                                            const int2 *__restrict__ row_range, float th, float c_lo, float c_hi,
+                                                            const float *__restrict__ N)
 {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -405,14 +437,22 @@ __global__ void __launch_bounds__(256) level0_batch_kernel(const float *__restri
             const int col = w * 64 + lane;
             const bool valid = col < rg.y && col != row;
             const float c = crow[valid ? col : row];
-            const float ac = fabsf(c);
             bool rm;
-            if (ac < c_lo)
-                rm = true;
-            else if (ac > c_hi && ac <= 1.0f)
-                rm = false;
+            if constexpr (HET)
+            {
+                const float nij = valid ? N[(size_t)row * n + col] : 4.0f;
+                rm = valid && het_pair_removed(c, nij, th);
+            }
             else
-                rm = z_below<false>(c, th);
+            {
+                const float ac = fabsf(c);
+                if (ac < c_lo)
+                    rm = true;
+                else if (ac > c_hi && ac <= 1.0f)
+                    rm = false;
+                else
+                    rm = z_below<false>(c, th);
+            }
             const unsigned long long m = __ballot(valid && !rm);
             if (lane == 0)
             {
@@ -425,9 +465,16 @@ __global__ void __launch_bounds__(256) level0_batch_kernel(const float *__restri
     if (lane == 0) deg[row] = d;
 }
 
-hipError_t launch_level0_batch(const float *C, unsigned long long *adj, unsigned long long *adj0, int *deg, int n, int words,
-                               const int2 *row_range, float th, hipStream_t st)
+// Ness != nullptr: per-pair thresholds th / sqrt(N_ij - 3) (th = the alpha/2 quantile), the batched het run
+hipError_t launch_level0_batch(const float *C, const float *Ness, unsigned long long *adj, unsigned long long *adj0, int *deg, int n,
+                               int words, const int2 *row_range, float th, hipStream_t st)
 {
+    const dim3 grid((unsigned)((n + 3) / 4)), block(256);
+    if (Ness)
+    {
+        hipLaunchKernelGGL(level0_batch_kernel<true>, grid, block, 0, st, C, adj, adj0, deg, n, words, row_range, th, 0.0f, 2.0f, Ness);
+        return hipGetLastError();
+    }
     float c_lo = 0.0f, c_hi = 2.0f;
     if (th >= kThMinFilter)
     {
@@ -435,8 +482,8 @@ hipError_t launch_level0_batch(const float *C, unsigned long long *adj, unsigned
         c_lo = (float)(tq * (1.0 - 5e-4));
         c_hi = (float)(tq * (1.0 + 5e-4));
     }
-    hipLaunchKernelGGL(level0_batch_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, C, adj, adj0, deg, n, words, row_range,
-                       th, c_lo, c_hi);
+    hipLaunchKernelGGL(level0_batch_kernel<false>, grid, block, 0, st, C, adj, adj0, deg, n, words, row_range, th, c_lo, c_hi,
+                       static_cast<const float *>(nullptr));
     return hipGetLastError();
 }
 

@@ -268,9 +268,9 @@ size_t sweep_vec_lds_bytes(int cls);
 hipError_t launch_level0(const float *C, const float *Ness, const int *Ginit, unsigned long long *adj, int n, int words,
                          float th, int *asym_flag, hipStream_t st);
 // block-diagonal level 0 of a batched Skeleton run: adjacency words of every row inside its block's column range, zeros
-// elsewhere, written to adj and adj0; also the level-1 degrees
-hipError_t launch_level0_batch(const float *C, unsigned long long *adj, unsigned long long *adj0, int *deg, int n, int words,
-                               const int2 *row_range, float th, hipStream_t st);
+// elsewhere, written to adj and adj0; also the level-1 degrees.  Ness (same allocation shape as C) = per-pair thresholds
+hipError_t launch_level0_batch(const float *C, const float *Ness, unsigned long long *adj, unsigned long long *adj0, int *deg, int n,
+                               int words, const int2 *row_range, float th, hipStream_t st);
 hipError_t launch_degree(const unsigned long long *adj, int *deg, int n, int words, unsigned long long *adj0, hipStream_t st);
 hipError_t launch_fill_nbr(const unsigned long long *adj, const int *off, int *nbr, unsigned long long *best, int n, int words,
                            int *wpre, const LevelCounters *cnt, const int2 *row_range, hipStream_t st);

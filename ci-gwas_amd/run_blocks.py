@@ -72,7 +72,8 @@ class BlockSet:
             self.h = None
 
     def set_het(self, het: bool = True) -> None:
-        """cusk_blockset_set_het: run_block takes the per-pair sample-size branch (`mps cusk ... het`); run_batch then fails"""
+        """cusk_blockset_set_het: run_block takes the per-pair sample-size branch (`mps cusk ... het`); run_batch then fails
+        (batches at per-pair sample sizes: run_batch_het)"""
         if lib().cusk_blockset_set_het(self.h, 1 if het else 0) != 0:
             raise RuntimeError("cusk_blockset_set_het failed")
         self.het = bool(het)
@@ -101,6 +102,17 @@ class BlockSet:
         rc = lib().cusk_blockset_run_batch(self.h, eng.h, ix.ctypes.data_as(C.c_void_p), len(ix), C.byref(res), C.byref(st))
         if rc != 0:
             raise RuntimeError(f"batch {list(blocks)[:4]}...: {lib().cusk_blockset_last_error().decode()}")
+        return BatchResult(res), st
+
+    def run_batch_het(self, eng: Engine, blocks):
+        """cusk_blockset_run_batch_het: run_batch with every block at per-pair sample sizes -- per block the result of
+        run_block on a set with set_het(True); works whatever set_het says -> (BatchResult, CuskBatchStats)"""
+        ix = np.ascontiguousarray(blocks, np.int32)
+        res = C.c_void_p()
+        st = CuskBatchStats()
+        rc = lib().cusk_blockset_run_batch_het(self.h, eng.h, ix.ctypes.data_as(C.c_void_p), len(ix), C.byref(res), C.byref(st))
+        if rc != 0:
+            raise RuntimeError(f"het batch {list(blocks)[:4]}...: {lib().cusk_blockset_last_error().decode()}")
         return BatchResult(res), st
 
     def run_block(self, eng: Engine, i: int, next_block: int = -1):
@@ -257,10 +269,11 @@ class _Queue:
 
 
 def run_rank_batched(bs, queue: "_Queue", device: int, batch_vars: int, options: dict | None = None, write_dir: str | None = None,
-                     engine_factory=None, inflight: int = 1):
+                     engine_factory=None, inflight: int = 1, het: bool = False):
     """The rank's blocks in batches of at most `batch_vars` padded variables, each batch through cusk_blockset_run_batch
-    (one level loop per stage for the whole batch).  -> (list of BatchResult, list of CuskBatchStats).  write_dir: the
-    files of a batch are written (by the library, cusk_batch_result_write) on a thread of their own beside the next batch."""
+    (one level loop per stage for the whole batch; het: cusk_blockset_run_batch_het, per-pair sample sizes).  -> (list of
+    BatchResult, list of CuskBatchStats).  write_dir: the files of a batch are written (by the library,
+    cusk_batch_result_write) on a thread of their own beside the next batch."""
     inflight = max(1, int(inflight))
     if engine_factory is not None:  # CPU tests of the batching / gather logic with a stand-in block set
         engines = [engine_factory() for _ in range(inflight)]
@@ -326,7 +339,7 @@ def run_rank_batched(bs, queue: "_Queue", device: int, batch_vars: int, options:
                     batch = next(gen, None)
                 if batch is None:
                     return
-                br, st = bs.run_batch(eng, batch)
+                br, st = bs.run_batch_het(eng, batch) if het else bs.run_batch(eng, batch)
                 with glock:
                     results.append(br)
                     stats.append(st)
@@ -462,7 +475,8 @@ def run_rank(bs, queue: _Queue, device: int, inflight: int = 1, options: dict | 
 
 def run_job(bs, outdir: str | None, device: int, inflight: int = 1, schedule: str = "lpt", collective_device=None,
             options: dict | None = None, group=None, engine_factory=None, store_key: str = "cusk_next_block",
-            stage: bool = True, writer: str = "rank0", batch_vars: int = 0, timings: dict | None = None, blockfile: str | None = None):
+            stage: bool = True, writer: str = "rank0", batch_vars: int = 0, timings: dict | None = None, blockfile: str | None = None,
+            het: bool = False):
     """One rank's part of the job (call on every rank of an initialised process group, or without one for a
     single-process run).  Returns (all results on rank 0 / None elsewhere, this rank's stats, assignment).
 
@@ -474,7 +488,10 @@ def run_job(bs, outdir: str | None, device: int, inflight: int = 1, schedule: st
     reads of them (indices, adjacency, correlations: no separating sets, a tenth of the bytes) is gathered to rank 0,
     which writes the MERGED skeleton `<outdir>/merged_blocks{_sam.mtx,_scm.mtx,.mdim,.ixs}` straight from memory
     (cusk_merge_packed): the job ends with the input of `cuskss-merged` / `sepselect` on disk and rank 0 writes four small
-    files instead of five per block."""
+    files instead of five per block.
+
+    het (with batch_vars > 0): the batches run at per-pair sample sizes (cusk_blockset_run_batch_het).  Without batches the
+    block set's own switch (BlockSet.set_het) decides, as before."""
     import torch.distributed as dist
 
     distributed = dist.is_available() and dist.is_initialized()
@@ -497,7 +514,7 @@ def run_job(bs, outdir: str | None, device: int, inflight: int = 1, schedule: st
         if writer == "merge" and blockfile is None:
             raise ValueError("writer = 'merge' needs the job's .blocks file")
         bres, bstats = run_rank_batched(bs, queue, device, batch_vars, options, write_dir=outdir if writer in ("local", "merge") else None,
-                                        engine_factory=engine_factory, inflight=inflight)
+                                        engine_factory=engine_factory, inflight=inflight, het=het)
         done = sorted(b for r in bres for b in r.block_indices)
         t1 = time.perf_counter()
         if writer == "local":
@@ -592,10 +609,21 @@ def parse_args(argv=None):
                          "whole batch (default 16384); 0: one block per engine run")
     ap.add_argument("--het", action="store_true",
                     help="every block at per-pair sample sizes (`mps cusk ... het`: phenotypes with NA entries); runs one "
-                         "block per engine run (--batch-vars 0), the batched run has no such form")
+                         "block per engine run (--batch-vars 0) unless --het-batch-vars asks for batches")
+    ap.add_argument("--het-batch-vars", type=int, default=0, metavar="V",
+                    help="implies --het: blocks are run in batches of at most V (padded) variables at per-pair sample sizes, one "
+                         "level loop per stage for the whole batch.  Stage one keeps the correlations AND the sample sizes of a "
+                         "batch in HBM: 2 x 4 x V^2 bytes (2.1 GB at 16384).  0 (default): --het runs one block per engine run; "
+                         "cannot be combined with a non-zero --batch-vars")
     ap.add_argument("--no-stage", action="store_true", help="do not keep the whole .bed in HBM; every block uploads its slice")
     ap.add_argument("--device", type=int, default=None, help="GPU of this rank (default LOCAL_RANK modulo the device count)")
     args = ap.parse_args(argv)
+    if args.het_batch_vars < 0:
+        ap.error("--het-batch-vars must not be negative")
+    if args.het_batch_vars > 0:
+        if args.batch_vars not in (None, 0):
+            ap.error("--het-batch-vars batches at per-pair sample sizes: it cannot be combined with a non-zero --batch-vars")
+        args.het = True
     if args.het and args.batch_vars not in (None, 0):
         ap.error("--het runs one block per engine run: it cannot be combined with a non-zero --batch-vars")
     if args.batch_vars is None:
@@ -632,10 +660,11 @@ def main(argv=None):
     t_open = time.perf_counter() - t0
     # no per-level HIP events: nothing here reads the per-level kernel times, and every event costs the launch-bound
     # small blocks a few microseconds of device time
-    batch_vars = 0 if args.no_stage else max(0, args.batch_vars)
+    het_batch = args.het_batch_vars > 0 and not args.no_stage  # (batches need the inputs in HBM; else block by block)
+    batch_vars = 0 if args.no_stage else max(0, args.het_batch_vars if het_batch else args.batch_vars)
     writer = args.writer if (batch_vars > 0 or args.writer != "merge") else "rank0"  # (merge is part of the batched path)
     allr, stats, owned = run_job(bs, args.outdir, device, args.inflight, args.schedule, cdev, stage=not args.no_stage,
-                                 options={"timing": 0}, writer=writer, batch_vars=batch_vars, blockfile=args.blocks)
+                                 options={"timing": 0}, writer=writer, batch_vars=batch_vars, blockfile=args.blocks, het=het_batch)
     dt = time.perf_counter() - t0
     if batch_vars > 0:
         tests = sum(int(s.tests[0]) + int(s.tests[1]) for s in stats)

@@ -268,6 +268,18 @@ class Engine:
         self._batch = (lo.copy(), hi.copy())
         return Stats.of(st)
 
+    def run_skeleton_batch_het(self, C_dev: int, N_dev: int, n: int, lo, hi, th: float, maxlevel: int) -> Stats:
+        """cusk_run_skeleton_batch_het: the batched run with every test decided at the per-pair sample sizes N_dev (an n x n
+        float32 allocation like C_dev with every block's sizes on the diagonal, e.g. from `ess_square_batch`);
+        th = hetcor_threshold(alpha).  Results as run_skeleton_batch: adjacency_blocks, sepsets"""
+        lo = np.ascontiguousarray(lo, np.int32)
+        hi = np.ascontiguousarray(hi, np.int32)
+        st = CuskStats()
+        self._check(lib().cusk_run_skeleton_batch_het(self.h, C_dev, N_dev, int(n), len(lo), _ptr(lo), _ptr(hi),
+                                                      float(np.float32(th)), int(maxlevel), C.byref(st)))
+        self._batch = (lo.copy(), hi.copy())
+        return Stats.of(st)
+
     def adjacency_blocks(self) -> list:
         """per block of the last batched run its k x k int32 adjacency (cusk_result_adj_bits_blocks)"""
         lo, hi = self._batch
@@ -319,6 +331,22 @@ class Engine:
         if (mxp_ess is not None and mxp_ess.size != int(m) * int(p)) or (pxp_ess is not None and pxp_ess.size != int(p) * int(p)):
             raise ValueError("ess_square: mxp_ess must hold m * p values and pxp_ess p * p")
         self._check(lib().cusk_ess_square(self.h, _ptr(mxp_ess), _ptr(pxp_ess), int(m), int(p), float(np.float32(n_uniform)), N_dev))
+
+    def ess_square_batch(self, mxp_ess, pxp_ess, m, base, p: int, n_uniform: float, n: int, N_dev: int) -> None:
+        """cusk_ess_square_batch: `ess_square` for the blocks of a batch in one launch.  Block b = variables base[b] ..
+        base[b] + m[b] + p of the n x n allocation at N_dev (16-byte aligned); mxp_ess = the blocks' m[b] x p tables back
+        to back, pxp_ess = one p x p table per block.  Cells outside the diagonal blocks are not written"""
+        m = np.ascontiguousarray(m, np.int32)
+        base = np.ascontiguousarray(base, np.int32)
+        if m.shape != base.shape or m.ndim != 1:
+            raise ValueError("ess_square_batch: one marker count and one base per block")
+        mxp_ess = np.ascontiguousarray(mxp_ess, np.float32).reshape(-1) if int(m.sum()) * int(p) else None
+        pxp_ess = np.ascontiguousarray(pxp_ess, np.float32).reshape(-1) if int(p) else None
+        if (mxp_ess is not None and mxp_ess.size != int(m.sum()) * int(p)) or \
+                (pxp_ess is not None and pxp_ess.size != len(m) * int(p) * int(p)):
+            raise ValueError("ess_square_batch: mxp_ess must hold sum(m) * p values and pxp_ess p * p per block")
+        self._check(lib().cusk_ess_square_batch(self.h, _ptr(mxp_ess), _ptr(pxp_ess), len(m), _ptr(m), _ptr(base), int(p),
+                                                float(np.float32(n_uniform)), int(n), N_dev))
 
     def adjacency(self) -> np.ndarray:
         n = lib().cusk_result_n(self.h)

@@ -187,7 +187,7 @@ int cusk_run_hetcor(cusk_engine *e, const float *C_dev, const float *N_dev, floa
  * comparison is false and the edge stays.  There is no time index and no starting graph.  With every size equal to N the
  * result is that of cusk_run_skeleton with Th[l] = th / sqrt(N - l - 3) formed in that arithmetic.
  * Every level runs on the exact path.  Not supported, each an error with a message in cusk_last_error: an engine that is
- * row-sharded (cusk_engine_set_row_shard with world > 1), option "validate"; there is no batched form. */
+ * row-sharded (cusk_engine_set_row_shard with world > 1), option "validate".  Batched form: cusk_run_skeleton_batch_het. */
 int cusk_run_skeleton_het(cusk_engine *e, const float *C_dev, const float *N_dev, int n, float th, int maxlevel,
                           cusk_stats *stats);
 
@@ -204,6 +204,15 @@ int cusk_run_skeleton_het(cusk_engine *e, const float *C_dev, const float *N_dev
  * cusk_result_adj_bits_blocks, cusk_result_sepsets (x, y and set members are variable indices of the batch). */
 int cusk_run_skeleton_batch(cusk_engine *e, const float *C_dev, int n, int nblk, const int *lo, const int *hi,
                             const float *Th, int maxlevel, cusk_stats *stats);
+/* The batched run at per-pair sample sizes: the layout rules and result accessors of cusk_run_skeleton_batch
+ * (cusk_result_adj_bits_blocks[_tail], cusk_result_sepsets[_view]) with the decision rule of cusk_run_skeleton_het.  N_dev
+ * is an n x n allocation like C_dev (same leading dimension) that holds every block's sample-size matrix on the diagonal,
+ * bitwise symmetric inside the blocks (cusk_ess_square_batch, cusk_gather_rows); elements outside the diagonal blocks are
+ * never read.  th = cusk_hetcor_threshold(alpha).  Per block the result is that of cusk_run_skeleton_het on the block
+ * alone: level 0 takes the same verdict per pair, every later level runs on the same exact path.  Errors as
+ * cusk_run_skeleton_het: a row-sharded engine, option "validate", N_dev = NULL. */
+int cusk_run_skeleton_batch_het(cusk_engine *e, const float *C_dev, const float *N_dev, int n, int nblk, const int *lo,
+                                const int *hi, float th, int maxlevel, cusk_stats *stats);
 /* adjacency of the last batched run, block by block: rows lo..hi-1 of block b, each cut to the (hi - lo + 63) / 64
  * words of the block's own columns (bit j of a row = local variable j), blocks back to back.  out_host: room for
  * sum_b (hi[b] - lo[b]) * ((hi[b] - lo[b] + 63) / 64) words. */
@@ -330,6 +339,15 @@ int cusk_pair_counts(cusk_engine *e, const unsigned char *bed, const float *phen
  * Returns when the matrix is written. */
 int cusk_ess_square(cusk_engine *e, const float *mxp_ess, const float *pxp_ess, size_t m, size_t p, float n_uniform,
                     float *N_dev);
+/* cusk_ess_square for the blocks of a batch, in one launch: block b holds the variables base[b] .. base[b] + m[b] + p of
+ * the n x n allocation N_dev (leading dimension n) and receives the (m[b] + p)^2 values of cusk_ess_square in its diagonal
+ * block.  mxp_ess: the blocks' m[b] x p tables back to back; pxp_ess: one p x p table per block, back to back (the blocks
+ * share the phenotypes, but a size is formed from the correlation it comes with, which is the block's own).  Cells
+ * outside the diagonal blocks are NOT written: no kernel reads them.  Errors, each with a message: bases that are not
+ * ascending multiples of 64 (or blocks that overlap), a block that reaches beyond n, N_dev not 16-byte aligned.  Returns
+ * when the matrix is written. */
+int cusk_ess_square_batch(cusk_engine *e, const float *mxp_ess, const float *pxp_ess, int nblk, const int *m, const int *base,
+                          size_t p, float n_uniform, int n, float *N_dev);
 /* Host only.  The sample size the mxp / pxp loaders of `cuskss` make of a correlation and its standard error:
  * ((1 - r^2) / se)^2 with their float / double mix (marker_trait_summary_stats.cpp:161-164). */
 float cusk_ess_from_se(float r, float se);
@@ -462,8 +480,8 @@ int cusk_blockset_run_block_next(cusk_blockset *bs, cusk_engine *e, int block_in
 const char *cusk_blockset_last_error(void);
 /* het = 1: cusk_blockset_run_block / _run_block_next run every block at per-pair sample sizes (`mps cusk ... het`: counts of
  * complete observations from the genotypes and the .phen, cusk_run_skeleton_het for both stages, the prefilter at the
- * marker x trait sizes); cusk_blockset_run_batch then returns an error (the batched run has no such form).  Set it
- * before running blocks; not while other threads run blocks of the set. */
+ * marker x trait sizes); cusk_blockset_run_batch then returns an error (batches at per-pair sample sizes have an entry point
+ * of their own, cusk_blockset_run_batch_het).  Set it before running blocks; not while other threads run blocks of the set. */
 int cusk_blockset_set_het(cusk_blockset *bs, int het);
 /* Forgets what the block set keeps for engine e -- its device scratch (block matrices) and the state of a correlation
  * build started ahead -- and releases that memory.  Call before destroying an engine that ran blocks of this set when the
@@ -488,6 +506,15 @@ typedef struct cusk_batch_stats {
 } cusk_batch_stats;
 int cusk_blockset_run_batch(cusk_blockset *bs, cusk_engine *e, const int *block_indices, int nblocks,
                             cusk_batch_result **out, cusk_batch_stats *stats);
+/* The same at per-pair sample sizes: per block the result -- and every file -- of cusk_blockset_run_block on a set with
+ * cusk_blockset_set_het(1).  One count pass (cusk_pair_counts) serves the batch's markers, the sizes of every block go
+ * through the cusk_se_from_count -> cusk_ess_from_se chain, the prefilter is the het one, both stages run through
+ * cusk_run_skeleton_batch_het with the sizes on the diagonal of a second allocation (cusk_ess_square_batch; stage two:
+ * gathered by the index tables that gather the correlations).  Works on any block set, whatever cusk_blockset_set_het
+ * says.  Device memory: correlations and sizes, 2 x 4 x (padded variable count)^2 bytes for stage one.  The count and size
+ * phases are part of ms_corr. */
+int cusk_blockset_run_batch_het(cusk_blockset *bs, cusk_engine *e, const int *block_indices, int nblocks,
+                                cusk_batch_result **out, cusk_batch_stats *stats);
 int cusk_batch_result_count(const cusk_batch_result *r);                       /* blocks with a result */
 int cusk_batch_result_block_index(const cusk_batch_result *r, int i);          /* index of result i in the .blocks file */
 const cusk_block_result *cusk_batch_result_block(const cusk_batch_result *r, int i); /* borrowed; accessors below */
