@@ -694,3 +694,64 @@ def level1_star_case(n: int = 1301, hub: int = 3, seed: int = 1, N: int = 4096, 
     np.fill_diagonal(Cm, 1.0)
     info = {"hub": hub, "N": N, "alpha": alpha, "rho": rho, "pairs": [(int(j), int(k)) for j, k in strong]}
     return np.ascontiguousarray(Cm.astype(np.float32)), info
+
+
+# ---------------------------------------------------------------- per-pair sample sizes and removals at depth
+def het_sizes(n: int, seed: int, N0: float, lo: float = 0.5, symmetric: bool = True) -> np.ndarray:
+    """n x n float32 sample sizes floor(U(lo, 1) N0), one draw per ORDERED pair (default_rng(seed)).  symmetric: the
+    element-wise minimum with the transpose (a pair is observed on the individuals both orders share); otherwise the raw
+    draw, N[i, j] != N[j, i] almost everywhere -- no estimator produces that, it pins which of the two elements a kernel
+    reads.  The diagonal is part of the draw and is never read by a sweep."""
+    rng = np.random.default_rng(seed)
+    Nm = np.floor(rng.uniform(lo, 1.0, (n, n)) * float(N0))
+    if symmetric:
+        Nm = np.minimum(Nm, Nm.T)
+    return np.ascontiguousarray(Nm, np.float32)
+
+
+def deep_removal_case(levels=range(5, 15), seed: int = 0, N: int = 20000, extras: int = 2, extra_weight: float = 0.3,
+                      weak: float = 2.77, return_info: bool = False):
+    """Float32 sample correlation matrix (N individuals) with removals at every level in `levels`: for each k one group
+    of independent variables [w_1..w_extras, p_1..p_k] and three children
+
+        x  = s + extra_weight (w_1 + .. + w_extras) + e_x        s = (p_1 + .. + p_k) / sqrt(k)
+        y  = s + e_y
+        y' = s + g e_x + e_y'
+
+    Groups share nothing.  x, y and y' are pairwise dependent given any proper subset of the parents (one parent left out
+    keeps a partial correlation of about 1 / (k + 1), z sqrt(N) of 9 and more at N = 20000), so the edges x - y, x - y',
+    y - y' survive to level k and only the set of all k parents separates them there.  The children's noise is as large
+    as the parents' sum: y and y' are then weak proxies of it, and a parent stays dependent on x given both (with unit
+    noise against a sum of variance 14 the two proxies explain a single parent away at level 2).  The w's stay neighbours of x (real edges) and come before the parents in
+    x's list, so the parents are not the first set of x's row: the winning rank is above 0.  g is chosen so that the
+    population z of (x, y' | parents) is weak / sqrt(N): with weak = 2.77 between the cut-off of alpha = 0.01 at N
+    (2.58 / sqrt(N)) and at the 0.75 N that `het_sizes` averages to over the pairs of a deep test (2.97 / sqrt(N));
+    sampling noise (sd 1 / sqrt(N)) decides per seed and level on which side the estimate falls.  The largest row,
+    x of k = 14, has 14 + 2 + extras neighbours.
+    Returns Cm, with return_info also {k: dict(x, y, y2, parents, extras)} (variable indices)."""
+    rng = np.random.default_rng(seed)
+    levels = [int(k) for k in levels]
+    n = sum(k + extras + 3 for k in levels)
+    X = np.empty((n, N), np.float64)
+    info, base = {}, 0
+    vx = 1.0 + extras * extra_weight ** 2  # variance of x given its parents
+    rho = weak / np.sqrt(N)
+    g = rho * np.sqrt(vx) / np.sqrt(max(1.0 - rho * rho * vx, 1e-12))  # g / sqrt(vx (g^2 + 1)) = rho
+    for k in levels:
+        w = np.arange(base, base + extras)
+        p = np.arange(base + extras, base + extras + k)
+        x, y, y2 = base + extras + k, base + extras + k + 1, base + extras + k + 2
+        X[base:x] = rng.standard_normal((extras + k, N))
+        s = X[p].sum(0) / np.sqrt(k)
+        ex = rng.standard_normal(N)
+        X[x] = s + extra_weight * X[w].sum(0) + ex
+        X[y] = s + rng.standard_normal(N)
+        X[y2] = s + g * ex + rng.standard_normal(N)
+        info[k] = dict(x=int(x), y=int(y), y2=int(y2), parents=[int(v) for v in p], extras=[int(v) for v in w])
+        base = y2 + 1
+    Cm = np.corrcoef(X).astype(np.float32)
+    Cm = np.triu(Cm, 1)
+    Cm = Cm + Cm.T
+    np.fill_diagonal(Cm, 1.0)
+    Cm = np.ascontiguousarray(Cm, np.float32)
+    return (Cm, info) if return_info else Cm
