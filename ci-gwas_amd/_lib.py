@@ -145,6 +145,7 @@ SYMBOLS = {
     "cusk_blockset_run_block_next": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp), C.POINTER(CuskBlockStats)]),
     "cusk_blockset_last_error": (C.c_char_p, []),
     "cusk_blockset_set_het": (_i, [_vp, _i]),
+    "cusk_blockset_set_het_filter": (_i, [_vp, _i]),
     "cusk_blockset_release_engine": (None, [_vp, _vp]),
     "cusk_blockset_run_batch": (_i, [_vp, _vp, _vp, _i, C.POINTER(_vp), _vp]),
     "cusk_blockset_run_batch_het": (_i, [_vp, _vp, _vp, _i, C.POINTER(_vp), _vp]),

@@ -67,6 +67,9 @@ def _add_cusk(sub):
     p.add_argument("--het", action="store_true",
                    help="test every marker-trait and trait-trait pair of the block at the number of individuals it was "
                         "observed on (phenotypes with NA entries), as `cuskss-merged --bfiles --phen --het` does afterwards")
+    p.add_argument("--het-filter", action="store_true",
+                   help="with --het: levels >= 2 of both stages through the filter and the recheck queue instead of the exact "
+                        "path alone (`mps cusk ... het filter`); same output files")
     p.set_defaults(func=cusk)
 
 
@@ -196,9 +199,11 @@ def block(args):
 
 def cusk_argv(args) -> list[str]:
     """ci-gwas.py:404-420"""
+    if getattr(args, "het_filter", False) and not getattr(args, "het", False):
+        sys.exit("cusk: --het-filter applies to runs at per-pair sample sizes: give --het with it.")
     return [MPS_PATH, "cusk", args.phen, args.bfiles, args.blocks, str(args.alpha), str(args.max_level),
             str(args.max_level_two), str(args.max_depth), args.outdir, str(args.block_index)] + (
-                ["het"] if getattr(args, "het", False) else [])
+                ["het"] if getattr(args, "het", False) else []) + (["filter"] if getattr(args, "het_filter", False) else [])
 
 
 def sumstats_argv(args) -> list[str]:

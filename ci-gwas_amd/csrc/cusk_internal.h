@@ -129,6 +129,7 @@ struct cusk_engine
     // options (cusk_engine_set_option)
     int opt_fast = 1;
     int opt_validate = 0;
+    int opt_het_filter = 0;  // cusk_run_skeleton_het / _batch_het: levels >= 2 through the filter and the recheck queue (0: exact path only)
     int opt_corr_fp4 = 1;
     int opt_pair = 1;
     int opt_rows = 1;

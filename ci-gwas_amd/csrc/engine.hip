@@ -126,7 +126,8 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
     std::memset(&local, 0, sizeof(local));
     // per-pair sample sizes: hetcor with a matrix, or Skeleton's records with hetcor's thresholds (cusk_run_skeleton_het)
     const bool het = (a.Ness != nullptr);
-    const bool het0 = het && a.mode == 0;  // exact path only: no filter, no union-major sweep, no level-1 row / pair kernels
+    const bool het0 = het && a.mode == 0;  // no vectorised sweep, no level-1 row / pair kernels; union-major sweep only with het_filter
+    const bool het0_exact = het0 && e->opt_het_filter == 0;  // ... and no filter either: every level on the exact path
     const int last_level = std::min(kML, a.maxlevel);
     const bool sharded = e->shard_world > 1;
     if (sharded && !e->shard_fn) return fail(e, CUSK_ERR_ARG, "row sharding needs an exchange function");
@@ -195,6 +196,15 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
             // but the pMax read-out, which then needs the copy made here)
             if (a.mode == 0 && last_level < 1) CUSK_HIP(e, hipMemcpyAsync(e->adj0.p, e->adj.p, bm, hipMemcpyDeviceToDevice, s));
         }
+    }
+    // option het_filter: is the size matrix bitwise symmetric (inside the blocks of a batch)?  Launched with level 0, read with
+    // the round trip that follows it; only then may the deep levels be swept by unions at one threshold per union
+    const bool ness_checked = het0 && e->opt_het_filter != 0 && last_level >= 2;
+    bool ness_symmetric = false;
+    if (ness_checked)
+    {
+        *e->hflag = 0;
+        CUSK_HIP(e, launch_ess_symmetry(a.Ness, n, a.row_range, e->hflag, s));
     }
     CUSK_HIP(e, hipEventRecord(e->ev_l1[0], s));
     hp_mark("l0_enq");
@@ -278,7 +288,7 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
             if (pl.use_pair && !exact_only)
                 CUSK_HIP(e, launch_pair(a.mode, sp, pl.pair_lds, cs));
             else if (pl.tmaj && pl.use_fast && !exact_only)
-                CUSK_HIP(e, launch_sweep_tmaj(a.mode, l, sp, c, cs));
+                CUSK_HIP(e, launch_sweep_tmaj(a.mode, het, l, sp, c, cs));
             else if (pl.use_fast && !exact_only && !het && e->opt_vec && !e->opt_validate && c < kNumClasses - 1 &&
                      sweep_vec_lds_bytes(c) <= kLdsLimit && l < kVecMaxLevel)
                 CUSK_HIP(e, launch_sweep_vec(a.mode, l, sp, c, c == 0 ? e->opt_vec_threads : kThreads, cs));
@@ -463,7 +473,7 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
                 // deep levels by unions T = S + Y: single threshold, symmetric matrix (the inverse-based form has no
                 // meaning for the two orientations of an asymmetric input), filter certified for this threshold
                 plan[l].tmaj = (e->opt_fast != 0) && !plan[l].force_exact && l >= std::max(2, e->opt_tmaj_min_level) && l <= kML &&
-                               th_l >= kThMinFilter && !het && symmetric && !sharded;
+                               th_l >= kThMinFilter && (!het || ness_symmetric) && symmetric && !sharded;
                 if (plan[l].tmaj) plan[l].chunk0 = chunk;
             }
             pa.chunk0 = plan[l].chunk0;
@@ -502,6 +512,8 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
                 if (rc != CUSK_OK) return rc;
                 hp_mark("gate1");
                 symmetric = (e->hgate[1].sym == 0) || (e->opt_assume_symmetric != 0) || (a.row_range != nullptr);
+                // (the symmetry kernel ran before the level-1 plan on this stream: its store has landed)
+                ness_symmetric = ness_checked && (*reinterpret_cast<volatile int *>(e->hflag) == 0);
                 cap_edges = std::max<long long>(e->hgate[1].total_edges, 1);
                 maxdeg1 = e->hgate[1].maxdeg;
                 for (int k = 0; k < 2; k++)
@@ -564,7 +576,7 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
                 for (int c = 0; c < kNumClasses; c++) pl.nitems[c] = e->hgate[l].class_items[c];
                 pl.known_items = true;
             }
-            pl.use_fast = (e->opt_fast != 0) && (l >= 2) && !pl.force_exact && !het0;
+            pl.use_fast = (e->opt_fast != 0) && (l >= 2) && !pl.force_exact && !het0_exact;
             // 2. the neighbour lists (no host dependency)
             CUSK_HIP(e, launch_fill_nbr(e->adj.as<unsigned long long>(), off_l, e->nbr[cs].as<int>(),
                                         (a.mode == 0 && !pl.use_rows) ? e->best[cs].as<unsigned long long>() : nullptr, n, words,
@@ -945,6 +957,8 @@ extern "C" int cusk_engine_set_option(cusk_engine *e, const char *key, long long
         e->opt_fast = (int)value;
     else if (k == "validate")
         e->opt_validate = (int)value;
+    else if (k == "het_filter")
+        e->opt_het_filter = (int)value;
     else if (k == "corr_fp4")
         e->opt_corr_fp4 = (int)value;
     else if (k == "pair")
@@ -1121,8 +1135,8 @@ extern "C" int cusk_run_skeleton_batch(cusk_engine *e, const float *C_dev, int n
     return rc;
 }
 
-// The batched run at per-pair sample sizes: the het0 plan of run_levels (exact path only: no filter, no vectorised or
-// union-major sweep, no level-1 row / pair kernels) with row_range set -- level 0 by level0_batch_kernel<true>, which
+// The batched run at per-pair sample sizes: the het0 plan of run_levels (no vectorised or union-major sweep, no level-1
+// row / pair kernels; exact path only unless option het_filter is set) with row_range set -- level 0 by level0_batch_kernel<true>, which
 // also writes the level-0 copy and the degrees; from level 1 on the engine works on CSR rows, and the exact sweep reads
 // C[a * n + b] and N[a * n + b] at the stride of the allocation, inside the row's own block only.
 extern "C" int cusk_run_skeleton_batch_het(cusk_engine *e, const float *C_dev, const float *N_dev, int n, int nblk, const int *lo,
@@ -1133,7 +1147,7 @@ extern "C" int cusk_run_skeleton_batch_het(cusk_engine *e, const float *C_dev, c
     if (!N_dev) return fail(e, CUSK_ERR_ARG, "cusk_run_skeleton_batch_het: needs the sample-size matrix");
     if (e->shard_world > 1)
         return fail(e, CUSK_ERR_ARG, "cusk_run_skeleton_batch_het: a row-sharded engine is not supported (per-pair sample sizes run on one engine)");
-    if (e->opt_validate)
+    if (e->opt_validate && !e->opt_het_filter)
         return fail(e, CUSK_ERR_ARG, "cusk_run_skeleton_batch_het: option validate is not supported (every test already runs on the exact path)");
     RunArgs a{};
     a.mode = 0;
@@ -1258,7 +1272,9 @@ extern "C" int cusk_run_hetcor(cusk_engine *e, const float *C_dev, const float *
 }
 
 // Skeleton's outputs (lowest passing rank per slot, separating-set records, pMax) decided at hetcor's per-test thresholds.
-// The level loop is Skeleton's; every level runs on the exact path (sweep_exact.hip, MODE 0 / HET).
+// The level loop is Skeleton's; every level runs on the exact path (sweep_exact.hip, MODE 0 / HET).  With option
+// het_filter levels >= 2 go through the filter at the per-test threshold (sweep_fast.hip, MODE 0 / HET) and the tests it
+// cannot certify through the recheck queue, as in the other modes; levels 0 and 1, the records and pMax are unchanged.
 extern "C" int cusk_run_skeleton_het(cusk_engine *e, const float *C_dev, const float *N_dev, int n, float th, int maxlevel,
                                      cusk_stats *stats)
 {
@@ -1266,7 +1282,7 @@ extern "C" int cusk_run_skeleton_het(cusk_engine *e, const float *C_dev, const f
     if (!N_dev) return fail(e, CUSK_ERR_ARG, "cusk_run_skeleton_het: needs the sample-size matrix");
     if (e->shard_world > 1)
         return fail(e, CUSK_ERR_ARG, "cusk_run_skeleton_het: a row-sharded engine is not supported (per-pair sample sizes run on one engine)");
-    if (e->opt_validate)
+    if (e->opt_validate && !e->opt_het_filter)
         return fail(e, CUSK_ERR_ARG, "cusk_run_skeleton_het: option validate is not supported (every test already runs on the exact path)");
     e->batch_lo.clear();
     RunArgs a{};

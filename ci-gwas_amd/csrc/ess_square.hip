@@ -99,6 +99,29 @@ __global__ void __launch_bounds__(256) ess_square_batch_kernel(const float *__re
     for (size_t j = 4 * nvec + lane; j < nb; j += 64) dst[j] = ess_square_value(mx, px, m, p, n_uniform, i, j);
 }
 
+// Is the size matrix its own transpose, bit for bit?  One wave per row, the lanes over the columns right of the diagonal
+// inside the row's block (the whole row without row_range); a difference stores 1 into *flag (pinned host memory, set to
+// 0 by the host before the launch).  NaN payloads compare as bits, so a NaN diagonal or a mirrored NaN pair is symmetric.
+// The union-major sweep at per-pair sample sizes (sweep_tmaj.hip, HET) is planned only when the flag stays 0.
+__global__ void __launch_bounds__(256) ess_symmetry_kernel(const unsigned *__restrict__ N, int n, const int2 *__restrict__ row_range,
+                                                           int *flag)
+{
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= n) return;
+    const int2 rr = row_range ? row_range[row] : make_int2(0, n);
+    bool bad = false;
+    for (int j = max(rr.x, row + 1) + lane; j < rr.y; j += 64) bad |= N[(size_t)row * n + j] != N[(size_t)j * n + row];
+    if (bad) *reinterpret_cast<volatile int *>(flag) = 1;
+}
+
+hipError_t launch_ess_symmetry(const float *N, int n, const int2 *row_range, int *flag, hipStream_t st)
+{
+    hipLaunchKernelGGL(ess_symmetry_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, reinterpret_cast<const unsigned *>(N), n,
+                       row_range, flag);
+    return hipGetLastError();
+}
+
 static int ess_square_impl(cusk_engine *e, const float *mxp_ess, const float *pxp_ess, size_t m, size_t p, float n_uniform,
                            float *N_dev)
 {

@@ -3,7 +3,7 @@
 // Same positional argv contracts, stdout milestones, exit codes and output files as the
 // reference's native CLI (/root/reference/cusk/apps/mps.cpp:17-121, src/cli.cpp:194-346,
 // :432-678), so that ci-gwas.py (or this repo's cli shim) can call it unchanged:
-//   mps cusk   <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het]
+//   mps cusk   <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het] [filter]
 //   mps cuskss <mxm> <mxp> <mxp_se> <pxp> <pxp_se> <time_index> <block_index> <blockfile>
 //              <marker_indices> <alpha> <l1> <l2> <depth> <num_samples> <outdir>   ("NULL" = absent)
 // and two commands the reference does not have, for users who hold the genotypes (see SUMSTATS_USAGE):
@@ -35,12 +35,14 @@ namespace {
 const char *CUSK_USAGE = R"(
 Run the skeleton search on a single block of a block diagonal genomic covariance matrix.
 
-usage: mps cusk <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het]
+usage: mps cusk <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het] [filter]
 
 arguments:
     het             test every marker-trait and trait-trait pair at the number of individuals it was observed on (.phen
                     with NA entries): prefilter, both skeleton stages and the separating sets of the block; the sizes are
                     those `cuskss-bed ... het` uses for the same pairs.  Same five output files.
+    filter          (after het) levels >= 2 of both stages through the filter and the recheck queue instead of the exact
+                    path alone (engine option het_filter).  Same five output files.
 )";
 
 // wall-clock phase marks, printed as "[t] <phase>: <ms> ms" when CUSK_TIMING is set (tools/e2e_block.py)
@@ -71,7 +73,7 @@ int cmd_cusk(int argc, char **argv)
     std::cout << "Got args: \n.phen: " << in.phen_path << "\nbfiles: " << in.bfiles << "\n.blocks: " << in.block_path
               << "\nalpha: " << in.alpha << "\nmax_level: " << in.max_level << "\nmax_level_two: " << in.max_level_two
               << "\ndepth: " << in.depth << "\noutdir: " << outdir << "\nblock-index: " << block_index << std::endl;
-    if (in.het) std::cout << "het: per-pair sample sizes" << std::endl;
+    if (in.het) std::cout << "het: per-pair sample sizes" << (in.het_filter ? ", levels >= 2 through the filter" : "") << std::endl;
 
     PhaseTimer tm;
     check_path(outdir);

@@ -249,7 +249,9 @@ hipError_t launch_rec_compact(const int *rec_l, const int *rec_x, const int *rec
 // sweep_fast.hip
 hipError_t launch_sweep_fast(int mode, bool het, int L, bool validate, const SweepParams &p, int cls, hipStream_t st);
 // sweep_tmaj.hip: deep levels by the union T = S + Y (one inverse per l + 1 tests); work items count (l + 1)-subsets
-hipError_t launch_sweep_tmaj(int mode, int L, const SweepParams &p, int cls, hipStream_t st);
+hipError_t launch_sweep_tmaj(int mode, bool het, int L, const SweepParams &p, int cls, hipStream_t st);
+// N == N^T as bit patterns (inside each row's block when row_range is given): *flag = 1 on the first difference (ess_square.hip)
+hipError_t launch_ess_symmetry(const float *N, int n, const int2 *row_range, int *flag, hipStream_t st);
 // union-major levels, work decomposition shared by the plan kernel and the sweep: prefixes (the first l - 1 members of a
 // union, the last of them at list position s) per lane of a work item, so that an item holds about `chunk` unions
 __host__ __device__ inline int tmaj_prefixes_per_lane(int d, int s, unsigned long long chunk)

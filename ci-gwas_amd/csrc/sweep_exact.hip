@@ -231,7 +231,8 @@ hipError_t launch_recheck(int mode, bool het, int L, const SweepParams &p, hipSt
         auto k0 = recheck_kernel<LL, 0, false>;                                                   \
         auto k1 = recheck_kernel<LL, 1, true>;                                                    \
         auto k2 = recheck_kernel<LL, 1, false>;                                                   \
-        auto kf = (mode == 0) ? k0 : (het ? k1 : k2);                                             \
+        auto k3 = recheck_kernel<LL, 0, true>;                                                    \
+        auto kf = (mode == 0) ? (het ? k3 : k0) : (het ? k1 : k2);                                \
         if (lds > 64 * 1024)                                                                      \
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kf),                         \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \

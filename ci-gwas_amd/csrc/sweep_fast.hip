@@ -125,6 +125,9 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 {
                     if constexpr (HET)
                     {
+                        // A mean size that is NaN or not above L + 3 (sizes with NaN, 0 or negative entries among them) makes
+                        // the threshold NaN: both comparisons of verdict_z are then false and the test comes out kUnsure,
+                        // so the exact path decides it as it does today (its own NaN threshold keeps the edge).
                         float s = essS + ess_term(rv.eval(k2, d));
 #pragma unroll
                         for (int a = 0; a < L; a++) s += ess_term(rv.eval(idx[a], k2));
@@ -205,10 +208,10 @@ static hipError_t launch_fast_level(int mode, bool het, bool validate, const Swe
 {
     if (validate)
     {
-        if (mode == 0) return launch_fast_L<L, 0, false, true>(p, cls, st);
+        if (mode == 0) return het ? launch_fast_L<L, 0, true, true>(p, cls, st) : launch_fast_L<L, 0, false, true>(p, cls, st);
         return het ? launch_fast_L<L, 1, true, true>(p, cls, st) : launch_fast_L<L, 1, false, true>(p, cls, st);
     }
-    if (mode == 0) return launch_fast_L<L, 0, false, false>(p, cls, st);
+    if (mode == 0) return het ? launch_fast_L<L, 0, true, false>(p, cls, st) : launch_fast_L<L, 0, false, false>(p, cls, st);
     return het ? launch_fast_L<L, 1, true, false>(p, cls, st) : launch_fast_L<L, 1, false, false>(p, cls, st);
 }
 

@@ -89,10 +89,22 @@ __device__ __noinline__ double rho2_f64(const RV &rv, int d, const int *S, int k
 // level 10, two beyond (at three, levels 11 and 12 spilled 60 - 85 values into the loop and ran slower than level 13).
 // Occupancy beats spills here: two waves with 20-60 spilled values (a dozen scratch accesses per union in the hot loop)
 // ran 18.5 / 45.6 / 585 / 1,310 ms at levels 9 / 10 / 13 / 14, one wave less without spills 21.7 / 53.1 / 885 / 1,406.
-template <int L, int MODE, bool STAGED, bool VALIDATE>
+//
+// HET (Skeleton's records at per-pair sample sizes, option het_filter): the l + 1 tests of a union are all about the
+// variable set T + {X}, so they share the (l + 2)(l + 1) / 2 pairwise sizes, hence mean_ess, hence ONE threshold
+// lth = th / sqrt(mean_ess - l - 3) -- provided N[a][b] == N[b][a] (the engine plans this kernel only after
+// ess_symmetry_kernel found the size matrix bitwise symmetric).  The sum of truncated sizes accumulates over Q + {X} once per
+// prefix, plus c1's pairs once per c1, plus c2's pairs once per union.
+// Guard band, domain rho^2: verdict_z (ci_fast.h) certifies z < lth - dz or z > lth + dz with dz = lth kBeta / 2 + 2e-6.
+// z = atanh|rho| is increasing in rho^2, so the same two regions are rho^2 < tanh(lth - dz)^2 and
+// rho^2 > tanh(lth + dz)^2; these two images replace t2 (1 -+ kBeta) of the single-threshold form, nothing narrower.
+// tanh(x) = 1 - 2 / (exp(2x) + 1) in fp32 carries an absolute error of ~2.5e-7, an eighth of dz's absolute term; a
+// lower edge lth - dz <= 0 certifies no pass.  A NaN or non-positive radicand sets `ill`: all l + 1 tests are queued.
+template <int L, int MODE, bool HET, bool STAGED, bool VALIDATE>
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L <= 7 ? 4 : (L <= 10 ? 3 : 2))))
 sweep_tmaj_kernel(SweepParams p)
 {
+    static_assert(!HET || MODE == 0, "per-pair sample sizes: Skeleton's records only");
     static_assert(L >= 2 && L + 1 < kBinomStride, "T = S + Y has l + 1 members");
     constexpr int NT = L + 1;  // members of T
     constexpr int NQ = L - 1;  // members of Q = the first l - 1 of T; c1 = T[NQ], c2 = T[NQ + 1]
@@ -128,7 +140,7 @@ sweep_tmaj_kernel(SweepParams p)
     const long long it_cur = it;
     it = dynamic ? it + 1 : it + gridDim.x;
     const int2 item = p.items[it_cur];
-    RowView<MODE, false, STAGED> rv(p, item.x, smem);
+    RowView<MODE, HET, STAGED> rv(p, item.x, smem);
     rv.stage();
     const int d = rv.d;
     [[maybe_unused]] const int tiX = (MODE == 1) ? rv.tix(d) : 0;
@@ -209,6 +221,17 @@ sweep_tmaj_kernel(SweepParams p)
                 sXX = __builtin_fmaf(-gx[i], acc, sXX);
             }
         }
+        [[maybe_unused]] float essQ = 0.0f;  // truncated sizes of the pairs inside Q + {X}
+        if constexpr (HET)
+        {
+#pragma unroll
+            for (int a = 0; a < NQ; a++)
+            {
+                essQ += ess_term(rv.eval(idx[a], d));
+#pragma unroll
+                for (int b = 0; b < a; b++) essQ += ess_term(rv.eval(idx[a], idx[b]));
+            }
+        }
         [[maybe_unused]] int tiQ_top = 0, tiQ_second = 0, tiQ_count = 0;
         if constexpr (MODE == 1)
         {  // the two largest time indices among Q (with the multiplicity of the largest)
@@ -253,6 +276,13 @@ sweep_tmaj_kernel(SweepParams p)
             const float d1 = s11, r1 = __frcp_rn(d1), l31 = s1X * r1;
             const float sXX1 = __builtin_fmaf(-l31, s1X, sXX);  // Var(X | Q, c1)
             const bool ill1 = illQ || !(d1 >= kCondMin);
+            [[maybe_unused]] float ess1 = essQ;  // ... plus c1's pairs
+            if constexpr (HET)
+            {
+                ess1 += ess_term(rv.eval(c1, d));
+#pragma unroll
+                for (int a = 0; a < NQ; a++) ess1 += ess_term(rv.eval(c1, idx[a]));
+            }
             for (int c2 = c1 + 1; c2 < d; c2++)
             {
                 idx[NQ + 1] = c2;
@@ -281,9 +311,23 @@ sweep_tmaj_kernel(SweepParams p)
                 const float tt = __builtin_fmaf(-l21, s1X, s2X);
                 const float l32 = tt * r2;
                 const float d3 = __builtin_fmaf(-l32, tt, sXX1), r3 = __frcp_rn(d3);  // Var(X | T) = 1 / P_XX
-                const bool ill = ill1 || !(d2 >= kCondMin) || !(d3 >= kCondMin);
+                bool ill = ill1 || !(d2 >= kCondMin) || !(d3 >= kCondMin);
                 // P_tX and P_tt of every member t through z = L^-1 u_t:  u^T W u = sum z_i^2 / d_i,  (W u)_X = z_3 / d_3
-                const float hiX = t2hi * r3, loX = t2lo * r3;
+                float hiX = t2hi * r3, loX = t2lo * r3;
+                if constexpr (HET)
+                {  // the union's one threshold and the images of verdict_z's band on rho^2
+                    float es = ess1 + ess_term(rv.eval(c2, d)) + ess_term(rv.eval(c2, c1));
+#pragma unroll
+                    for (int a = 0; a < NQ; a++) es += ess_term(rv.eval(c2, idx[a]));
+                    const float rad = es / (float)((L + 2) * (L + 1) / 2) - (float)(L + 3);
+                    const float lth = p.th * __frsqrt_rn(rad);
+                    const float dz = lth * (0.5f * kBeta) + 2e-6f;
+                    const float zl = lth - dz;
+                    const float tl = 1.0f - 2.0f / (__expf(2.0f * zl) + 1.0f), tu = 1.0f - 2.0f / (__expf(2.0f * (lth + dz)) + 1.0f);
+                    ill = ill || !(rad > 0.0f) || !(lth == lth);
+                    loX = (zl > 0.0f) ? tl * tl * r3 : 0.0f;
+                    hiX = tu * tu * r3;
+                }
                 bool anytodo = ill;
                 float numv[NT], pyyv[NT];
 #pragma unroll
@@ -386,7 +430,13 @@ sweep_tmaj_kernel(SweepParams p)
                         for (int a = 0; a < L; a++) S[a] = idx[a < j ? a : a + 1];
                         const double r2d = rho2_f64<L>(rv, d, S, idx[j]);
                         const bool pj = (passm >> j) & 1u;
-                        if (pj ? !(r2d < (double)t2 * (1.0 - 0.25 * (double)kBeta)) : !(r2d > (double)t2 * (1.0 + 0.25 * (double)kBeta))) nbad++;
+                        if constexpr (HET)
+                        {  // against the exact per-test threshold of this test, in double precision
+                            const double tq = tanh((double)rv.template ess_threshold_exact<L>(idx[j], S));
+                            if (pj ? !(r2d < tq * tq) : !(r2d > tq * tq)) nbad++;
+                        }
+                        else if (pj ? !(r2d < (double)t2 * (1.0 - 0.25 * (double)kBeta)) : !(r2d > (double)t2 * (1.0 + 0.25 * (double)kBeta)))
+                            nbad++;
                     }
                 }
                 if ((passm | unsurem) != 0u)
@@ -426,15 +476,15 @@ sweep_tmaj_kernel(SweepParams p)
     flush_counters(s_cnt, p.slots, ntests, nsub, MODE == 1 ? nrem : 0ull, nbad);
 }
 
-template <int L, int MODE>
+template <int L, int MODE, bool HET>
 static hipError_t launch_tmaj_L(const SweepParams &p, int cls, hipStream_t st)
 {
     if (cls < kNumClasses - 1)
     {
-        const size_t lds = lds_layout(kClassCap[cls], false).total;
+        const size_t lds = lds_layout(kClassCap[cls], HET).total;
         // the validating build exists for the Skeleton engine's staged classes (a device function call in the kernel
         // costs the other builds their registers)
-        auto kfn = (MODE == 0 && p.validate) ? sweep_tmaj_kernel<L, MODE, true, (MODE == 0)> : sweep_tmaj_kernel<L, MODE, true, false>;
+        auto kfn = (MODE == 0 && p.validate) ? sweep_tmaj_kernel<L, MODE, HET, true, (MODE == 0)> : sweep_tmaj_kernel<L, MODE, HET, true, false>;
         if (lds > 64 * 1024)
         {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -446,7 +496,7 @@ static hipError_t launch_tmaj_L(const SweepParams &p, int cls, hipStream_t st)
     }
     else
     {
-        auto kfn = sweep_tmaj_kernel<L, MODE, false, false>;
+        auto kfn = sweep_tmaj_kernel<L, MODE, HET, false, false>;
         const unsigned grid = (unsigned)std::min<long long>(persistent_grid(reinterpret_cast<const void *>(kfn), kThreads, 16),
                                                             std::max<long long>(p.grid_cap, 1));
         hipLaunchKernelGGL(kfn, dim3(grid), dim3(kThreads), 16, st, p);
@@ -454,12 +504,14 @@ static hipError_t launch_tmaj_L(const SweepParams &p, int cls, hipStream_t st)
     return hipGetLastError();
 }
 
-hipError_t launch_sweep_tmaj(int mode, int L, const SweepParams &p, int cls, hipStream_t st)
+hipError_t launch_sweep_tmaj(int mode, bool het, int L, const SweepParams &p, int cls, hipStream_t st)
 {
     switch (L)
     {
 #define CUSK_CASE(LL) \
-    case LL: return mode == 0 ? launch_tmaj_L<LL, 0>(p, cls, st) : launch_tmaj_L<LL, 1>(p, cls, st);
+    case LL:          \
+        if (mode == 0) return het ? launch_tmaj_L<LL, 0, true>(p, cls, st) : launch_tmaj_L<LL, 0, false>(p, cls, st); \
+        return launch_tmaj_L<LL, 1, false>(p, cls, st);
         CUSK_CASE(2)
         CUSK_CASE(3)
         CUSK_CASE(4)

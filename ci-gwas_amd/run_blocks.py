@@ -78,6 +78,14 @@ class BlockSet:
             raise RuntimeError("cusk_blockset_set_het failed")
         self.het = bool(het)
 
+    def set_het_filter(self, on: bool = True) -> None:
+        """cusk_blockset_set_het_filter: the runs at per-pair sample sizes (run_block after set_het, run_batch_het) set
+        engine option het_filter on their engine -- levels >= 2 of both stages through the filter and the recheck queue
+        (`mps cusk ... het filter`); same files"""
+        if lib().cusk_blockset_set_het_filter(self.h, 1 if on else 0) != 0:
+            raise RuntimeError("cusk_blockset_set_het_filter failed")
+        self.het_filter = bool(on)
+
     def markers(self, i: int) -> int:
         return int(lib().cusk_blockset_block_markers(self.h, i))
 
@@ -476,7 +484,7 @@ def run_rank(bs, queue: _Queue, device: int, inflight: int = 1, options: dict | 
 def run_job(bs, outdir: str | None, device: int, inflight: int = 1, schedule: str = "lpt", collective_device=None,
             options: dict | None = None, group=None, engine_factory=None, store_key: str = "cusk_next_block",
             stage: bool = True, writer: str = "rank0", batch_vars: int = 0, timings: dict | None = None, blockfile: str | None = None,
-            het: bool = False):
+            het: bool = False, het_filter: bool = False):
     """One rank's part of the job (call on every rank of an initialised process group, or without one for a
     single-process run).  Returns (all results on rank 0 / None elsewhere, this rank's stats, assignment).
 
@@ -491,8 +499,12 @@ def run_job(bs, outdir: str | None, device: int, inflight: int = 1, schedule: st
     files instead of five per block.
 
     het (with batch_vars > 0): the batches run at per-pair sample sizes (cusk_blockset_run_batch_het).  Without batches the
-    block set's own switch (BlockSet.set_het) decides, as before."""
+    block set's own switch (BlockSet.set_het) decides, as before.  het_filter: the runs at per-pair sample sizes, batched
+    or block by block, go through the filter at levels >= 2 (BlockSet.set_het_filter); same files."""
     import torch.distributed as dist
+
+    if het_filter:
+        bs.set_het_filter(True)
 
     distributed = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if distributed else 0
@@ -615,6 +627,9 @@ def parse_args(argv=None):
                          "level loop per stage for the whole batch.  Stage one keeps the correlations AND the sample sizes of a "
                          "batch in HBM: 2 x 4 x V^2 bytes (2.1 GB at 16384).  0 (default): --het runs one block per engine run; "
                          "cannot be combined with a non-zero --batch-vars")
+    ap.add_argument("--het-filter", action="store_true",
+                    help="with --het or --het-batch-vars: levels >= 2 of both stages through the filter and the recheck queue "
+                         "instead of the exact path alone (`mps cusk ... het filter`); same files")
     ap.add_argument("--no-stage", action="store_true", help="do not keep the whole .bed in HBM; every block uploads its slice")
     ap.add_argument("--device", type=int, default=None, help="GPU of this rank (default LOCAL_RANK modulo the device count)")
     args = ap.parse_args(argv)
@@ -626,6 +641,8 @@ def parse_args(argv=None):
         args.het = True
     if args.het and args.batch_vars not in (None, 0):
         ap.error("--het runs one block per engine run: it cannot be combined with a non-zero --batch-vars")
+    if args.het_filter and not args.het:
+        ap.error("--het-filter applies to runs at per-pair sample sizes: give --het or --het-batch-vars with it")
     if args.batch_vars is None:
         args.batch_vars = 0 if args.het else 16384
     return args
@@ -664,7 +681,8 @@ def main(argv=None):
     batch_vars = 0 if args.no_stage else max(0, args.het_batch_vars if het_batch else args.batch_vars)
     writer = args.writer if (batch_vars > 0 or args.writer != "merge") else "rank0"  # (merge is part of the batched path)
     allr, stats, owned = run_job(bs, args.outdir, device, args.inflight, args.schedule, cdev, stage=not args.no_stage,
-                                 options={"timing": 0}, writer=writer, batch_vars=batch_vars, blockfile=args.blocks, het=het_batch)
+                                 options={"timing": 0}, writer=writer, batch_vars=batch_vars, blockfile=args.blocks, het=het_batch,
+                                 het_filter=args.het_filter)
     dt = time.perf_counter() - t0
     if batch_vars > 0:
         tests = sum(int(s.tests[0]) + int(s.tests[1]) for s in stats)

@@ -128,7 +128,7 @@ const char *cusk_last_error(const cusk_engine *e);
  * cusk_corr_build on the FP4 matrix pipe; 0: the int8 MFMA form), "corr_popcount" (default 0; 1: bit-plane AND/popcount
  * cross-check kernels instead of the matrix cores), "corr_mxp_f32" (default 0: SNP x trait sums on the bf16 matrix pipe with every
  * trait value split exactly into three bf16 pieces; 1: the f32 matrix instructions of rounds 1-2), "assume_symmetric" (default 0: level 0 verifies C == C^T bitwise;
- * 1: the caller guarantees it, e.g. a matrix written by cusk_corr_build), "queue_capacity" (recheck queue entries, default 4Mi), "chunk" (combination ranks per work item, default 2048), "timing" (HIP events for cusk_stats: 0 total_ms only; 1, the default, around every level's sweep: kernel_ms, and level_ms = end of the previous level's sweep to the end of this one's; 2 also level start / end: level_ms = plan to finaliser; 3 only the pair around the level-1 row kernel: main_kernel_ms[1] -- every event costs a few microseconds of device time), "chunk0" (conditioning sets per work item of the first degree class, default 512), "tmaj_min_level" (first level swept by unions T = S + Y, one inverse per l + 1 tests: default 6, 99 = never; single threshold and symmetric matrix only), "tmaj_validate_stride" (with "validate": the union-major sweep checks the unions whose per-lane count is a multiple of this power of two against double precision; default 1 = all), "hostprof" (1: host-side phase marks of every run on stderr), "max_staged_classes" (test hook: at most this many degree classes keep their sub-matrix in LDS; 0 sends every row through the kernels of the unstaged class), "chunk0_low" (work-item size of the first degree class at levels 2-4, default 256), "vec_threads" (workgroup size of the vectorised sweep for the first degree class: 64, 128 or 256; default 64), "lookahead" (levels the host enqueues ahead of the level counters it has seen, default 2; every kernel checks its level's gate on the device), "sync2" (default 1: the host reads level 2's gate record -- class counts, maximum degree -- before it enqueues that level's sweeps, so that degree classes that turn out empty are not launched at levels >= 2; 0: enqueue ahead on the level-1 degree bound), "item_capacity" (work items per degree class and level the buffers hold before the engine grows them and takes the level up again, default 1Mi), "sepselect_ws_bytes" (HBM work space of
+ * 1: the caller guarantees it, e.g. a matrix written by cusk_corr_build), "queue_capacity" (recheck queue entries, default 4Mi), "chunk" (combination ranks per work item, default 2048), "timing" (HIP events for cusk_stats: 0 total_ms only; 1, the default, around every level's sweep: kernel_ms, and level_ms = end of the previous level's sweep to the end of this one's; 2 also level start / end: level_ms = plan to finaliser; 3 only the pair around the level-1 row kernel: main_kernel_ms[1] -- every event costs a few microseconds of device time), "chunk0" (conditioning sets per work item of the first degree class, default 512), "tmaj_min_level" (first level swept by unions T = S + Y, one inverse per l + 1 tests: default 6, 99 = never; single threshold and symmetric matrix only), "tmaj_validate_stride" (with "validate": the union-major sweep checks the unions whose per-lane count is a multiple of this power of two against double precision; default 1 = all), "hostprof" (1: host-side phase marks of every run on stderr), "max_staged_classes" (test hook: at most this many degree classes keep their sub-matrix in LDS; 0 sends every row through the kernels of the unstaged class), "chunk0_low" (work-item size of the first degree class at levels 2-4, default 256), "vec_threads" (workgroup size of the vectorised sweep for the first degree class: 64, 128 or 256; default 64), "lookahead" (levels the host enqueues ahead of the level counters it has seen, default 2; every kernel checks its level's gate on the device), "sync2" (default 1: the host reads level 2's gate record -- class counts, maximum degree -- before it enqueues that level's sweeps, so that degree classes that turn out empty are not launched at levels >= 2; 0: enqueue ahead on the level-1 degree bound), "item_capacity" (work items per degree class and level the buffers hold before the engine grows them and takes the level up again, default 1Mi), "het_filter" (default 0: cusk_run_skeleton_het / cusk_run_skeleton_batch_het run every level on the exact path; 1: their levels >= 2 go through the filter at the per-test threshold and the recheck queue like the other modes, "fast" = 0 still selects the exact path, and "validate" is accepted), "sepselect_ws_bytes" (HBM work space of
  * cusk_sepselect_greedy for candidate lists too long for LDS, default 4 GiB; such pairs run in batches of what fits). */
 int cusk_engine_set_option(cusk_engine *e, const char *key, long long value);
 /* Host only, no device needed: the workgroup size level 1's row-streaming kernel runs with when a row of C takes
@@ -187,7 +187,13 @@ int cusk_run_hetcor(cusk_engine *e, const float *C_dev, const float *N_dev, floa
  * comparison is false and the edge stays.  There is no time index and no starting graph.  With every size equal to N the
  * result is that of cusk_run_skeleton with Th[l] = th / sqrt(N - l - 3) formed in that arithmetic.
  * Every level runs on the exact path.  Not supported, each an error with a message in cusk_last_error: an engine that is
- * row-sharded (cusk_engine_set_row_shard with world > 1), option "validate".  Batched form: cusk_run_skeleton_batch_het. */
+ * row-sharded (cusk_engine_set_row_shard with world > 1), option "validate".  Batched form: cusk_run_skeleton_batch_het.
+ * Option "het_filter" = 1: levels >= 2 run through the register-Cholesky filter at a float estimate of the per-test
+ * threshold; what it cannot certify (guard band, conditioning guard, NaN threshold) is queued and decided on the exact
+ * path, a queue overflow redoes the level there (exact_fallbacks), and "validate" counts certified verdicts the exact
+ * per-test threshold contradicts.  Levels >= "tmaj_min_level" are swept by unions with one threshold per union when N_dev
+ * is bitwise symmetric (checked on the device, inside the blocks of a batch), else by conditioning set.  Adjacency,
+ * records and pMax are those of the exact path either way. */
 int cusk_run_skeleton_het(cusk_engine *e, const float *C_dev, const float *N_dev, int n, float th, int maxlevel,
                           cusk_stats *stats);
 
@@ -210,7 +216,8 @@ int cusk_run_skeleton_batch(cusk_engine *e, const float *C_dev, int n, int nblk,
  * bitwise symmetric inside the blocks (cusk_ess_square_batch, cusk_gather_rows); elements outside the diagonal blocks are
  * never read.  th = cusk_hetcor_threshold(alpha).  Per block the result is that of cusk_run_skeleton_het on the block
  * alone: level 0 takes the same verdict per pair, every later level runs on the same exact path.  Errors as
- * cusk_run_skeleton_het: a row-sharded engine, option "validate", N_dev = NULL. */
+ * cusk_run_skeleton_het: a row-sharded engine, option "validate" (without "het_filter"), N_dev = NULL.  Option
+ * "het_filter" as for cusk_run_skeleton_het. */
 int cusk_run_skeleton_batch_het(cusk_engine *e, const float *C_dev, const float *N_dev, int n, int nblk, const int *lo,
                                 const int *hi, float th, int maxlevel, cusk_stats *stats);
 /* adjacency of the last batched run, block by block: rows lo..hi-1 of block b, each cut to the (hi - lo + 63) / 64
@@ -483,6 +490,10 @@ const char *cusk_blockset_last_error(void);
  * marker x trait sizes); cusk_blockset_run_batch then returns an error (batches at per-pair sample sizes have an entry point
  * of their own, cusk_blockset_run_batch_het).  Set it before running blocks; not while other threads run blocks of the set. */
 int cusk_blockset_set_het(cusk_blockset *bs, int het);
+/* on = 1: the runs of this set at per-pair sample sizes (cusk_blockset_run_block with cusk_blockset_set_het(1),
+ * cusk_blockset_run_batch_het) set engine option "het_filter" = 1 on the engine they are given, for both stages
+ * (`mps cusk ... het filter`).  Same files; 0 (default) leaves the engine's option as it is.  Set it before running blocks. */
+int cusk_blockset_set_het_filter(cusk_blockset *bs, int on);
 /* Forgets what the block set keeps for engine e -- its device scratch (block matrices) and the state of a correlation
  * build started ahead -- and releases that memory.  Call before destroying an engine that ran blocks of this set when the
  * set outlives it (cusk_blockset_close releases everything anyway). */
