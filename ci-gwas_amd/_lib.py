@@ -91,6 +91,7 @@ SYMBOLS = {
     "cusk_engine_stream": (_vp, [_vp]),
     "cusk_engine_bind_thread": (_i, [_vp]),
     "cusk_engine_device": (_i, [_vp]),
+    "cusk_engine_level1_form": (_i, [_vp]),
     "cusk_engine_set_row_shard": (_i, [_vp, _i, _i, _vp, _vp, _i]),
     "cusk_run_skeleton": (_i, [_vp, _vp, _i, _vp, _i, C.POINTER(CuskStats)]),
     "cusk_run_hetcor": (_i, [_vp, _vp, _vp, _f, _vp, _i, _f, _i, _vp, C.POINTER(CuskStats)]),
@@ -146,6 +147,7 @@ SYMBOLS = {
     "cusk_blockset_last_error": (C.c_char_p, []),
     "cusk_blockset_set_het": (_i, [_vp, _i]),
     "cusk_blockset_set_het_filter": (_i, [_vp, _i]),
+    "cusk_blockset_set_het_rows": (_i, [_vp, _i]),
     "cusk_blockset_release_engine": (None, [_vp, _vp]),
     "cusk_blockset_run_batch": (_i, [_vp, _vp, _vp, _i, C.POINTER(_vp), _vp]),
     "cusk_blockset_run_batch_het": (_i, [_vp, _vp, _vp, _i, C.POINTER(_vp), _vp]),

@@ -70,6 +70,9 @@ def _add_cusk(sub):
     p.add_argument("--het-filter", action="store_true",
                    help="with --het: levels >= 2 of both stages through the filter and the recheck queue instead of the exact "
                         "path alone (`mps cusk ... het filter`); same output files")
+    p.add_argument("--het-rows", action="store_true",
+                   help="with --het: level 1 of both stages on the row-streaming kernel at per-pair sample sizes instead of the "
+                        "exact sweep (`mps cusk ... het rows`); same output files")
     p.set_defaults(func=cusk)
 
 
@@ -201,9 +204,12 @@ def cusk_argv(args) -> list[str]:
     """ci-gwas.py:404-420"""
     if getattr(args, "het_filter", False) and not getattr(args, "het", False):
         sys.exit("cusk: --het-filter applies to runs at per-pair sample sizes: give --het with it.")
+    if getattr(args, "het_rows", False) and not getattr(args, "het", False):
+        sys.exit("cusk: --het-rows applies to runs at per-pair sample sizes: give --het with it.")
     return [MPS_PATH, "cusk", args.phen, args.bfiles, args.blocks, str(args.alpha), str(args.max_level),
             str(args.max_level_two), str(args.max_depth), args.outdir, str(args.block_index)] + (
-                ["het"] if getattr(args, "het", False) else []) + (["filter"] if getattr(args, "het_filter", False) else [])
+                ["het"] if getattr(args, "het", False) else []) + (["filter"] if getattr(args, "het_filter", False) else []) + (
+                    ["rows"] if getattr(args, "het_rows", False) else [])
 
 
 def sumstats_argv(args) -> list[str]:

@@ -108,6 +108,8 @@ struct cusk_engine
     void *res_pinned = nullptr;    // cusk_result_sepsets_view: x, y, S of the records
     size_t res_pinned_cap = 0;
     cusk::DevBuf rv, rpos, sel, wpre;  // level 1, row-streaming kernel: C[X, adj(X)] and {Y, reverse position, off, deg} per CSR slot
+    cusk::DevBuf nv;                   // ... its HET form: ess_term(N[X, adj(X)]) beside rv
+    int level1_form = -1;              // cusk_engine_level1_form: kernel of level 1 in the last run (-1: no level 1 ran)
     long long nrec = 0;
     // pinned host mirrors
     cusk::LevelCounters *hcnt = nullptr;   // kLevels entries
@@ -130,6 +132,7 @@ struct cusk_engine
     int opt_fast = 1;
     int opt_validate = 0;
     int opt_het_filter = 0;  // cusk_run_skeleton_het / _batch_het: levels >= 2 through the filter and the recheck queue (0: exact path only)
+    int opt_het_rows = 0;    // cusk_run_skeleton_het / _batch_het: level 1 on the HET form of the row kernel when the size matrix is bitwise symmetric
     int opt_corr_fp4 = 1;
     int opt_pair = 1;
     int opt_rows = 1;

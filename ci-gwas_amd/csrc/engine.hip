@@ -122,11 +122,12 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
     e->mode = a.mode;
     e->have_result = false;
     e->nrec = 0;
+    e->level1_form = -1;
     cusk_stats local;
     std::memset(&local, 0, sizeof(local));
     // per-pair sample sizes: hetcor with a matrix, or Skeleton's records with hetcor's thresholds (cusk_run_skeleton_het)
     const bool het = (a.Ness != nullptr);
-    const bool het0 = het && a.mode == 0;  // no vectorised sweep, no level-1 row / pair kernels; union-major sweep only with het_filter
+    const bool het0 = het && a.mode == 0;  // no vectorised sweep, no level-1 pair kernel; row kernel only with het_rows, union-major sweep only with het_filter
     const bool het0_exact = het0 && e->opt_het_filter == 0;  // ... and no filter either: every level on the exact path
     const int last_level = std::min(kML, a.maxlevel);
     const bool sharded = e->shard_world > 1;
@@ -199,9 +200,11 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
     }
     // option het_filter: is the size matrix bitwise symmetric (inside the blocks of a batch)?  Launched with level 0, read with
     // the round trip that follows it; only then may the deep levels be swept by unions at one threshold per union
+    // option het_rows: the same check decides whether level 1 may run on the row kernel (both tests of a pair at one threshold)
     const bool ness_checked = het0 && e->opt_het_filter != 0 && last_level >= 2;
-    bool ness_symmetric = false;
-    if (ness_checked)
+    const bool ness_checked_rows = het0 && e->opt_het_rows != 0 && last_level >= 1;
+    bool ness_symmetric = false, ness_symmetric_rows = false;
+    if (ness_checked || ness_checked_rows)
     {
         *e->hflag = 0;
         CUSK_HIP(e, launch_ess_symmetry(a.Ness, n, a.row_range, e->hflag, s));
@@ -220,6 +223,7 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
     int level_out = (a.maxlevel < 0) ? 0 : last_level + 1;
     int levels_swept = 0;
     bool rows_timed = false;
+    int level1_form = -1;  // cusk_engine_level1_form: the kernel level 1 was enqueued on
     // Gate of a level's finalisation and of the next level's plan: "the recheck queue held every uncertain test".  A
     // level that is run (or redone) on the exact path has no queue: ~0.
     unsigned long long qcap_gate[kLevels];
@@ -239,12 +243,14 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
             CUSK_HIP(e, launch_level1_rows(a.mode, e->opt_validate != 0, pl.filter_ok && e->opt_fast != 0, sp, e->rv.as<float>(),
                                            e->rpos.p, e->sel.as<unsigned>(), e->wpre.as<int>(), e->opt_timing ? e->ev_main[0] : nullptr,
                                            e->opt_timing ? e->ev_main[1] : nullptr, e->shard_rank, e->shard_world, e->opt_l1_threads, e->opt_l1_lds_row != 0, sharded,
-                                           a.time_index != nullptr, (a.mode == 1) ? dcanon + (size_t)l * kCounterSlots : nullptr, s));
+                                           a.time_index != nullptr, (a.mode == 1) ? dcanon + (size_t)l * kCounterSlots : nullptr, s,
+                                           het0 ? e->nv.as<float>() : nullptr, &level1_form));
             rows_timed = true;
             return CUSK_OK;
         }
         // classes that can hold work at this level: a row of degree d belongs to the first class with d <= cap, and no
         // degree exceeds the level-1 maximum
+        if (l == 1) level1_form = (pl.use_pair && !exact_only) ? 1 : 0;
         int nonempty = 0;
         bool may[kNumClasses];
         for (int c = 0; c < kNumClasses; c++)
@@ -514,6 +520,7 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
                 symmetric = (e->hgate[1].sym == 0) || (e->opt_assume_symmetric != 0) || (a.row_range != nullptr);
                 // (the symmetry kernel ran before the level-1 plan on this stream: its store has landed)
                 ness_symmetric = ness_checked && (*reinterpret_cast<volatile int *>(e->hflag) == 0);
+                ness_symmetric_rows = ness_checked_rows && (*reinterpret_cast<volatile int *>(e->hflag) == 0);
                 cap_edges = std::max<long long>(e->hgate[1].total_edges, 1);
                 maxdeg1 = e->hgate[1].maxdeg;
                 for (int k = 0; k < 2; k++)
@@ -555,6 +562,13 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
                 pl.pair_lds = (size_t)maxdeg1 * 20 + 16;
                 pl.use_pair = !het && symmetric && (e->opt_pair != 0) && pl.pair_lds <= 64 * 1024;
                 pl.use_rows = !het && symmetric && (e->opt_pair != 0) && (e->opt_rows != 0);
+                // per-pair sample sizes: the HET form of the row kernel, opt-in (option het_rows) and only on a bitwise symmetric
+                // size matrix; "fast" = 0 keeps level 1 on the exact sweep as it keeps the deeper levels there
+                if (het0 && ness_symmetric_rows && symmetric && (e->opt_fast != 0) && (e->opt_pair != 0) && (e->opt_rows != 0))
+                {
+                    pl.use_rows = true;
+                    CUSK_HIP(e, e->nv.ensure(sizeof(float) * ((size_t)cap_edges + 4)));
+                }
                 if (pl.use_rows) CUSK_HIP(e, e->wpre.ensure(sizeof(int) * (size_t)n * words));
                 if (pl.use_pair && !pl.use_rows)
                 {  // the pair kernel counts its work items differently: plan again (option rows = 0 only)
@@ -804,6 +818,7 @@ static int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st)
     local.total_ms = ms;
     local.level = level_out;
     e->last_levels = levels_swept;
+    e->level1_form = levels_swept >= 1 ? level1_form : -1;
     e->nrec = 0;  // the dense record list is produced on request (materialize_records)
     e->have_result = true;
     if (st) *st = local;
@@ -918,7 +933,7 @@ extern "C" void cusk_engine_destroy(cusk_engine *e)
         if (ph) (void)hipHostFree(ph);
     if (e->batch_pinned) (void)hipHostFree(e->batch_pinned);
     for (DevBuf *b : {&e->adj, &e->adj0, &e->deg, &e->binom, &e->counters, &e->ti, &e->queue,
-                      &e->rv, &e->rpos, &e->sel, &e->wpre, &e->rec_x, &e->rec_y, &e->rec_l, &e->rec_s, &e->den_x, &e->den_y, &e->den_l,
+                      &e->rv, &e->nv, &e->rpos, &e->sel, &e->wpre, &e->rec_x, &e->rec_y, &e->rec_l, &e->rec_s, &e->den_x, &e->den_y, &e->den_l,
                       &e->den_z, &e->den_s, &e->den_counts, &e->den_off, &e->off1, &e->planblk, &e->scratch_a, &e->scratch_b, &e->bed_dev, &e->phen_dev,
                       &e->mean_dev, &e->std_dev, &e->planes, &e->mxp_dev, &e->mxp_bq})
         b->release();
@@ -959,6 +974,8 @@ extern "C" int cusk_engine_set_option(cusk_engine *e, const char *key, long long
         e->opt_validate = (int)value;
     else if (k == "het_filter")
         e->opt_het_filter = (int)value;
+    else if (k == "het_rows" && (value == 0 || value == 1))
+        e->opt_het_rows = (int)value;
     else if (k == "corr_fp4")
         e->opt_corr_fp4 = (int)value;
     else if (k == "pair")
@@ -1031,6 +1048,7 @@ extern "C" int cusk_engine_set_row_shard(cusk_engine *e, int rank, int world, cu
 extern "C" const char *cusk_last_error(const cusk_engine *e) { return e ? e->err.c_str() : "no engine"; }
 extern "C" void *cusk_engine_stream(const cusk_engine *e) { return e ? (void *)e->stream : nullptr; }
 extern "C" int cusk_engine_device(const cusk_engine *e) { return e ? e->device : -1; }
+extern "C" int cusk_engine_level1_form(const cusk_engine *e) { return e ? e->level1_form : -1; }
 extern "C" int cusk_engine_bind_thread(cusk_engine *e)
 {
     if (!e) return CUSK_ERR_ARG;

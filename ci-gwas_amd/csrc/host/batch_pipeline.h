@@ -278,6 +278,7 @@ inline void run_cusk_batch(cusk_engine *e, const CuskInputs &in, const StagedInp
         mark("ess_square");
         bs.ms_corr += ms_since(t);
         if (in.het_filter) cusk_engine_set_option(e, "het_filter", 1);  // (stays set for stage two)
+        if (in.het_rows) cusk_engine_set_option(e, "het_rows", 1);      // (likewise)
         if (cusk_run_skeleton_batch_het(e, scr.C.p, scr.Ness.p, (int)n1, K, lo1.data(), hi1.data(), in.th_het, in.max_level, &bs.stage[0]) !=
             CUSK_OK)
             engine_die("Skeleton (het, batch)", e);

@@ -219,6 +219,13 @@ extern "C" int cusk_blockset_set_het_filter(cusk_blockset *bs, int on)
     return CUSK_OK;
 }
 
+extern "C" int cusk_blockset_set_het_rows(cusk_blockset *bs, int on)
+{
+    if (!bs) return CUSK_ERR_ARG;
+    bs->in.het_rows = on != 0;
+    return CUSK_OK;
+}
+
 extern "C" void cusk_blockset_release_engine(cusk_blockset *bs, cusk_engine *e)
 {
     if (!bs || !e) return;

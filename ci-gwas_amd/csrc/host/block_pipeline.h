@@ -461,6 +461,9 @@ struct CuskInputs
     // `mps cusk ... het filter`: the het runs set engine option het_filter (levels >= 2 through the filter and the
     // recheck queue instead of the exact path alone); same results
     bool het_filter = false;
+    // `mps cusk ... het rows`: the het runs set engine option het_rows (level 1 on the row kernel at per-pair sample sizes
+    // when the size matrix is symmetric); same results
+    bool het_rows = false;
     MappedFile bed;
     // all markers' means / stds, read once when several blocks are run from one process (empty: line-range reads)
     std::vector<float> means_all, stds_all;
@@ -496,8 +499,9 @@ struct CuskInputs
     size_t first_marker(const Block &b) const { return bim.start_of(b.chr) + b.first; }
 };
 
-// argv of `mps cusk` (cli.cpp:432-456 plus the optional trailing `het` or `het filter`): false = too few arguments (the caller prints the
-// usage text and exits with 1); an unknown trailing argument or one too many dies with a message (status 1)
+// argv of `mps cusk` (cli.cpp:432-456 plus the optional trailing `het`, which the words `filter` and `rows` may follow in
+// either order, each at most once): false = too few arguments (the caller prints the usage text and exits with 1); an
+// unknown or repeated trailing argument, or one too many, dies with a message (status 1)
 inline bool parse_cusk_args(int argc, char **argv, CuskInputs &in, std::string &outdir, int &block_index)
 {
     if (argc < 11) return false;
@@ -512,9 +516,17 @@ inline bool parse_cusk_args(int argc, char **argv, CuskInputs &in, std::string &
     block_index = std::stoi(argv[10]);
     in.het = argc > 11;
     if (in.het && std::string(argv[11]) != "het") die(std::string("cusk: unknown trailing argument ") + argv[11]);
-    in.het_filter = argc > 12;
-    if (in.het_filter && std::string(argv[12]) != "filter") die(std::string("cusk: unknown trailing argument ") + argv[12]);
-    if (argc > 13) die(std::string("cusk: unknown trailing argument ") + argv[13]);
+    in.het_filter = in.het_rows = false;
+    for (int i = 12; i < argc; i++)
+    {
+        const std::string w(argv[i]);
+        if (w == "filter" && !in.het_filter)
+            in.het_filter = true;
+        else if (w == "rows" && !in.het_rows)
+            in.het_rows = true;
+        else
+            die(std::string("cusk: unknown trailing argument ") + argv[i]);
+    }
     return true;
 }
 
@@ -708,6 +720,7 @@ inline bool run_cusk_block(cusk_engine *e, const CuskInputs &in, int block_index
     if (in.het)
     {
         if (in.het_filter) cusk_engine_set_option(e, "het_filter", 1);  // (stays set for stage two)
+        if (in.het_rows) cusk_engine_set_option(e, "het_rows", 1);      // (likewise)
         if (cusk_run_skeleton_het(e, scr.C.p, scr.Ness.p, (int)n, in.th_het, in.max_level, &st) != CUSK_OK) engine_die("Skeleton (het)", e);
     }
     else if (cusk_run_skeleton(e, scr.C.p, (int)n, in.Th, in.max_level, &st) != CUSK_OK)

@@ -3,7 +3,7 @@
 // Same positional argv contracts, stdout milestones, exit codes and output files as the
 // reference's native CLI (/root/reference/cusk/apps/mps.cpp:17-121, src/cli.cpp:194-346,
 // :432-678), so that ci-gwas.py (or this repo's cli shim) can call it unchanged:
-//   mps cusk   <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het] [filter]
+//   mps cusk   <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het] [filter] [rows]
 //   mps cuskss <mxm> <mxp> <mxp_se> <pxp> <pxp_se> <time_index> <block_index> <blockfile>
 //              <marker_indices> <alpha> <l1> <l2> <depth> <num_samples> <outdir>   ("NULL" = absent)
 // and two commands the reference does not have, for users who hold the genotypes (see SUMSTATS_USAGE):
@@ -35,7 +35,7 @@ namespace {
 const char *CUSK_USAGE = R"(
 Run the skeleton search on a single block of a block diagonal genomic covariance matrix.
 
-usage: mps cusk <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het] [filter]
+usage: mps cusk <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het] [filter] [rows]
 
 arguments:
     het             test every marker-trait and trait-trait pair at the number of individuals it was observed on (.phen
@@ -43,6 +43,8 @@ arguments:
                     those `cuskss-bed ... het` uses for the same pairs.  Same five output files.
     filter          (after het) levels >= 2 of both stages through the filter and the recheck queue instead of the exact
                     path alone (engine option het_filter).  Same five output files.
+    rows            (after het, before or after filter) level 1 of both stages on the row-streaming kernel at per-pair
+                    sample sizes (engine option het_rows).  Same five output files.
 )";
 
 // wall-clock phase marks, printed as "[t] <phase>: <ms> ms" when CUSK_TIMING is set (tools/e2e_block.py)
@@ -73,7 +75,8 @@ int cmd_cusk(int argc, char **argv)
     std::cout << "Got args: \n.phen: " << in.phen_path << "\nbfiles: " << in.bfiles << "\n.blocks: " << in.block_path
               << "\nalpha: " << in.alpha << "\nmax_level: " << in.max_level << "\nmax_level_two: " << in.max_level_two
               << "\ndepth: " << in.depth << "\noutdir: " << outdir << "\nblock-index: " << block_index << std::endl;
-    if (in.het) std::cout << "het: per-pair sample sizes" << (in.het_filter ? ", levels >= 2 through the filter" : "") << std::endl;
+    if (in.het) std::cout << "het: per-pair sample sizes" << (in.het_filter ? ", levels >= 2 through the filter" : "")
+                          << (in.het_rows ? ", level 1 on the row kernel" : "") << std::endl;
 
     PhaseTimer tm;
     check_path(outdir);
@@ -95,6 +98,11 @@ int cmd_cusk(int argc, char **argv)
     std::string stem;
     BlockStats bs;
     const bool kept = run_cusk_block(e, in, block_index, scratch, out, stem, bs, &std::cout);
+    // (a level 1 that ran on the row kernel forms no conditioning sets: subsets[1] = 0 beside tests[1] > 0)
+    if (in.het_rows)
+        for (int k = 0; k < 2; k++)
+            std::cout << "het rows: stage " << (k + 1) << " level 1 " << (bs.stage[k].tests[1] > 0 && bs.stage[k].subsets[1] == 0 ? "on the row kernel" : "not on the row kernel")
+                      << ", " << bs.stage[k].rechecks[1] << " of " << bs.stage[k].tests[1] << " tests sent to the exact form" << std::endl;
     if (tm.on)
     {
         std::cout << "[t] inputs (bed slice, means, stds): " << bs.ms_inputs << " ms\n[t] correlation build (H2D + kernels + mxp D2H): "

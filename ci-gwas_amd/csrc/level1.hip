@@ -4,6 +4,7 @@
 #include <cmath>
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 #include "ci_exact.h"
 #include "ci_fast.h"
@@ -235,6 +236,19 @@ __global__ void level1_prep_kernel(const float *__restrict__ C, const int *__res
     }
 }
 
+// HET sibling of level1_prep_kernel: nv = ess_term(N[row, Y]) per CSR slot, the sizes N[X, .] of the row kernel's tests
+// (int-truncated once here, as ess_term does it, instead of in every step of the sweep).  The row kernel runs only on a
+// bitwise symmetric N, so N[row, Y] stands for the N[Y][row] that ess_threshold_exact reads.
+__global__ void level1_prep_nv_kernel(const float *__restrict__ N, const int *__restrict__ off, const int *__restrict__ nbr, float *nv,
+                                      int n, const LevelCounters *cnt)
+{
+    const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= n || !cnt->active) return;
+    const int o0 = off[row], d = off[row + 1] - o0;
+    for (int k = lane; k < d; k += 64) nv[o0 + k] = ess_term(N[(size_t)row * n + nbr[o0 + k]]);
+}
+
 struct RowsParams
 {
     const float *rv;
@@ -244,6 +258,10 @@ struct RowsParams
     int has_ti;      // hetcor engine: a time index was given (else every index is 0 and the rule excludes nothing)
     float beta;      // half-width of the level-1 guard band on rho^2 (level1_beta)
     int shard_rank, shard_world;  // row-sharded runs: this engine streams the rows ya with ya % world == rank
+    // HET form (per-pair sample sizes, level1_rows2_kernel<..., HET = true>)
+    const float *nv;  // per CSR slot: ess_term(N[X, Y]), gathered at level start next to rv (level1_prep_nv_kernel)
+    float th2;        // th^2: the filter's estimate of a test's threshold starts from th^2 / (mean size - 4)
+    int nrow_off;     // LDSROW: the row of N follows the row of C in LDS at this distance (floats, a multiple of 4)
 };
 
 // Half-width of the level-1 guard band on rho^2.  Unlike the deeper levels (Cholesky against SVD, conditioning-dependent:
@@ -327,6 +345,10 @@ struct RowsStep2
     int yb0, yb1;
     float ra;
     rows_f2 c;
+    // HET: the three sizes of the lane's two pairs, int-truncated: N[X, yb] (both positions), N[X, ya], N[ya, yb]
+    rows_f2u nbu;
+    float na;
+    rows_f2 nab;
 };
 
 // LDSROW: the columns [ya, n) of the workgroup's row of C are staged in LDS once (coalesced 16-byte loads) and the
@@ -334,15 +356,50 @@ struct RowsStep2
 // (40 KB each at n = 10,020, five per CU) evict each other and the per-edge streams -- 2.3 GB of L2 fills per launch for
 // a 401 MB matrix, which is what bounds the kernel once the instruction count is down (37 % vector issue).  THREADS grows
 // with n so that the CU keeps its waves when fewer rows fit into its 160 KB (launch_level1_rows).
-template <int MODE, bool VALIDATE, int THREADS, bool LDSROW>
+//
+// HET (cusk_run_skeleton_het / _batch_het with option het_rows, MODE 0 only): every test is decided at the sample sizes of
+// its own three pairs.  The two tests of a lane's pair, (X; ya | yb) and (X; yb | ya), are about the same variables, and on
+// a bitwise symmetric N (the engine checks: ess_symmetry_kernel) they read the same three sizes: N[X, yb] arrives with the
+// list entries in stage A (rp.nv beside rp.rv), N[X, ya] per segment in the place of X in s_seg (MODE 0 never reads X), and
+// N[ya, yb] lies in row ya of N, staged in LDS behind the row of C (LDSROW, already int-truncated) or read through L1/L2.
+// The exact threshold of a test is RowView::ess_threshold_exact<1>: s = (N[Y][X] + N[S][X]) + N[S][Y] in float, me = s / 3,
+// lth = (float)((double)th / sqrt((double)me - 1 - 3)).  Float addition commutes, so the two tests of a pair share s and lth.
+// The filter judges both at a float estimate of tanh(lth)^2 that needs no square root:
+//     u = th^2 / (me - 4) = lth^2,   tanh(x)^2 = u P(u)^2,   P(u) = tanh(x) / x = 1 - u/3 + 2u^2/15 - 17u^3/315 + 62u^4/2835 - ...
+// and certifies a verdict only where  me - 4 >= 64,  kHetUMin <= u <= 1/16  (lth between kThMinFilter, below which no filter
+// of this engine is certified, and 1/4; a mean size of a few hundred and more at the usual alpha).  Everything else -- small
+// or huge sizes, a NaN or non-positive radicand -- is "not sure" and goes to level1_exact at the exact lth.
+// Relative error of the estimate against tanh(lth)^2 of the exact float lth, 2^-24 = 6e-8 per rounding:
+//   s:      the same three terms; summed here in the order of ess_threshold_exact, but the bound does not rely on it: two
+//           additions of integers that can pass 2^24 at biobank sizes, any order within 2 x 6e-8 of any other  1.2e-7
+//   me:     s * fl(1/3) against fl(s / 3): constant, product, the exact form's quotient                          1.8e-7
+//   me - 4: both carried over with me / (me - 4) <= 68/64, plus the subtraction's rounding                      3.8e-7
+//   u:      fl(th^2) from the host, v_rcp_f32 (1 ulp), the product                                      + 2.4e-7 = 6.2e-7
+//   lth:    the exact form computes in double (1e-16) and rounds lth to float once: 6e-8 on lth, 1.2e-7 on lth^2  7.4e-7
+//   tanh^2: d ln(u P^2) / d ln u lies in (0, 1] (P falls with u), so the 7.4e-7 carry over at most unchanged;
+//           the series cut behind u^4 (alternating, next term 8.9e-3 u^5 <= 8.5e-9 of P); Horner in float, every inner
+//           error scaled by u <= 1/16: 1e-7 on P; the square and the product with u                      + 3.4e-7 = 1.1e-6
+// The band is level1_beta's own expression at the test's t = tanh(lth) (16 (2 (2.4e-7 + 5.6e-8 / t) + 3e-7), with
+// 1 / t = v_rsq_f32 of the estimate; u >= kHetUMin keeps it below kBeta: 9.2e-4 at t = 2e-3) widened by kHetWiden = 4e-6,
+// more than three times the 1.1e-6 above: a lane the filter certifies at the estimate lies outside level1_beta's band
+// around the exact tanh(lth)^2.  tests/test_cusk_het_rows_formats.py restates estimate and band in numpy.
+constexpr float kHetUMin = 4.1e-6f;   // lth^2 >= kThMinFilter^2 = 4e-6 with the estimate's error to spare
+constexpr float kHetUMax = 0.0625f;   // lth <= 1/4: range of the series
+constexpr float kHetDMin = 64.0f;     // me - 4
+constexpr float kHetWiden = 4.0e-6f;
+constexpr float kHetBeta0 = 16.0f * (2.0f * 2.4e-7f + 3.0e-7f) + kHetWiden;  // level1_beta's terms that do not depend on t
+constexpr float kHetBeta1 = 16.0f * 2.0f * 5.6e-8f;                          // ... times 1 / t
+
+template <int MODE, bool VALIDATE, int THREADS, bool LDSROW, bool HET = false>
 __global__ void __launch_bounds__(THREADS) level1_rows2_kernel(SweepParams p, RowsParams rp)
 {
+    static_assert(!HET || MODE == 0, "per-pair sample sizes: Skeleton mode only");
     constexpr int kRowsThreads = THREADS, kRowsChunk = THREADS;
     __shared__ int4 s_seg[kRowsChunk];  // {slot of (X, a), a, C[X, row] bits, X}
     __shared__ int s_dx[kRowsChunk];    // degree of X
     __shared__ int s_pre[kRowsChunk + 1];
     __shared__ int s_wtot[2][kRowsThreads / 64];
-    __shared__ unsigned long long s_cnt[2];  // executed tests, filter violations (VALIDATE)
+    __shared__ unsigned long long s_cnt[HET ? 3 : 2];  // executed tests, filter violations (VALIDATE), HET: tests the filter did not certify
     extern __shared__ __attribute__((aligned(16))) float s_row[];  // LDSROW: s_row[col + sh] = C[ya, col], col >= ya
     const int n = p.n;
     // (Rows to XCDs, tried in round 3: XCD x takes the x-th and (15 - x)-th sixteenth of the rows instead of every eighth
@@ -380,9 +437,10 @@ __global__ void __launch_bounds__(THREADS) level1_rows2_kernel(SweepParams p, Ro
     if (!act) return;
     const int d = o1 - o0;
     if (d == 0) return;
-    if (tid < 2) s_cnt[tid] = 0ull;
+    if (tid < (HET ? 3 : 2)) s_cnt[tid] = 0ull;
     int4 m = make_int4(0, 0, 0, 0);
     float mra = 0.0f;
+    [[maybe_unused]] float mna = 0.0f;  // HET: ess_term(N[X, row])
     if (tid < d) m = rp.meta[o0 + tid];
     if constexpr (LDSROW)
     {
@@ -408,6 +466,8 @@ __global__ void __launch_bounds__(THREADS) level1_rows2_kernel(SweepParams p, Ro
         asm volatile("" ::: "memory");  // the row's requests stay between the record load and its dependent gather
     }
     if (tid < d) mra = rp.rv[m.z + m.y];  // C[X, row]
+    if constexpr (HET)
+        if (tid < d) mna = rp.nv[m.z + m.y];
     if constexpr (LDSROW)
     {
         *reinterpret_cast<rows_f4 *>(s_row + i0) = v0;
@@ -427,12 +487,35 @@ __global__ void __launch_bounds__(THREADS) level1_rows2_kernel(SweepParams p, Ro
             *reinterpret_cast<rows_f4 *>(s_row + i3) = v3;
         }
         // visible to every wave after the first barrier of the staging round below
+        if constexpr (HET)
+        {  // the same columns of row ya of N (same allocation shape and alignment as C: checked by the launcher), int-truncated
+            // once here; they land rp.nrow_off floats behind the row of C
+            const float *nbase = p.Ness + (gbase - p.C);
+            float *s_nrow = s_row + rp.nrow_off;
+            auto trunc4 = [](rows_f4 v) -> rows_f4 { return rows_f4{ess_term(v.x), ess_term(v.y), ess_term(v.z), ess_term(v.w)}; };
+            for (int i = i_first; i < i_end; i += kStep * 4)
+            {
+                i0 = min(i, i_last), i1 = min(i + kStep, i_last), i2 = min(i + 2 * kStep, i_last), i3 = min(i + 3 * kStep, i_last);
+                v0 = __builtin_nontemporal_load(reinterpret_cast<const rows_f4 *>(nbase + i0));
+                v1 = __builtin_nontemporal_load(reinterpret_cast<const rows_f4 *>(nbase + i1));
+                v2 = __builtin_nontemporal_load(reinterpret_cast<const rows_f4 *>(nbase + i2));
+                v3 = __builtin_nontemporal_load(reinterpret_cast<const rows_f4 *>(nbase + i3));
+                *reinterpret_cast<rows_f4 *>(s_nrow + i0) = trunc4(v0);
+                *reinterpret_cast<rows_f4 *>(s_nrow + i1) = trunc4(v1);
+                *reinterpret_cast<rows_f4 *>(s_nrow + i2) = trunc4(v2);
+                *reinterpret_cast<rows_f4 *>(s_nrow + i3) = trunc4(v3);
+            }
+        }
     }
+    [[maybe_unused]] const float *nrow = nullptr;  // HET, gather form: row ya of N through L1/L2
+    if constexpr (HET && !LDSROW) nrow = p.Ness + (size_t)ya * n;
     [[maybe_unused]] int tiA = 0;
     if constexpr (MODE == 1) tiA = p.time_index[ya];
     const bool use_filter = rp.use_filter != 0;
     const float th = p.th, t2 = p.t2, beta = rp.beta;
+    [[maybe_unused]] const float th2 = rp.th2;
     unsigned ntests = 0, viol = 0;
+    [[maybe_unused]] unsigned nslow = 0;  // HET: tests sent to the exact form because the filter was not sure (cusk_stats.rechecks[1])
     const bool count_by_segment = (MODE == 0) || !rp.has_ti;
     for (int kc = 0; kc < d; kc += kRowsChunk)
     {
@@ -474,7 +557,10 @@ __global__ void __launch_bounds__(THREADS) level1_rows2_kernel(SweepParams p, Ro
         }
         if (plen > 0)
         {
-            s_seg[pos0 + pos - 1] = make_int4(m.z + m.y, m.y, __float_as_int(mra), m.x);
+            if constexpr (HET)
+                s_seg[pos0 + pos - 1] = make_int4(m.z + m.y, m.y, __float_as_int(mra), __float_as_int(mna));
+            else
+                s_seg[pos0 + pos - 1] = make_int4(m.z + m.y, m.y, __float_as_int(mra), m.x);
             s_dx[pos0 + pos - 1] = m.w;
             s_pre[pos0 + pos - 1] = pre0 + pre - plen;
         }
@@ -483,6 +569,7 @@ __global__ void __launch_bounds__(THREADS) level1_rows2_kernel(SweepParams p, Ro
         {  // next round, in flight meanwhile
             m = rp.meta[o0 + kc + kRowsChunk + tid];
             mra = rp.rv[m.z + m.y];
+            if constexpr (HET) mna = rp.nv[m.z + m.y];
         }
         __syncthreads();
         // ---- this wave's contiguous share of the flat range ----
@@ -519,12 +606,16 @@ __global__ void __launch_bounds__(THREADS) level1_rows2_kernel(SweepParams p, Ro
             st.b = e.y + r;
             st.in1 = st.in0 && (st.b + 1 < dX);
             st.ra = __int_as_float(e.z);
-            st.X = e.w;
+            if constexpr (HET)
+                st.na = __int_as_float(e.w);
+            else
+                st.X = e.w;
             st.first_lane = max(0, seg0 - base);
             st.ia = (unsigned)e.x;
             st.ib = (unsigned)(e.x + r);
             st.nb = *reinterpret_cast<const rows_i2u *>(reinterpret_cast<const char *>(p.nbr) + (st.ib << 2));
             st.rbu = *reinterpret_cast<const rows_f2u *>(reinterpret_cast<const char *>(rp.rv) + (st.ib << 2));
+            if constexpr (HET) st.nbu = *reinterpret_cast<const rows_f2u *>(reinterpret_cast<const char *>(rp.nv) + (st.ib << 2));
         };
         auto stage_b = [&](RowsStep2 &st) {
             st.yb0 = st.nb.x;
@@ -538,6 +629,19 @@ __global__ void __launch_bounds__(THREADS) level1_rows2_kernel(SweepParams p, Ro
             {
                 st.c.x = ld32<float>(crow, (unsigned)st.yb0);
                 st.c.y = ld32<float>(crow, (unsigned)st.yb1);
+            }
+            if constexpr (HET)
+            {
+                if constexpr (LDSROW)
+                {
+                    st.nab.x = s_row[st.yb0 + sh + rp.nrow_off];
+                    st.nab.y = s_row[st.yb1 + sh + rp.nrow_off];
+                }
+                else
+                {
+                    st.nab.x = ess_term(ld32<float>(nrow, (unsigned)st.yb0));
+                    st.nab.y = ess_term(ld32<float>(nrow, (unsigned)st.yb1));
+                }
             }
         };
         auto stage_c = [&](const RowsStep2 &cur) {
@@ -570,11 +674,33 @@ __global__ void __launch_bounds__(THREADS) level1_rows2_kernel(SweepParams p, Ro
             const rows_f2 h00a = one - (rb * rb), h01a = rav - (rb * c);
             const float h00b = 1.0f - (ra * ra);
             const rows_f2 h00bv = {h00b, h00b}, h01b = rb - (rav * c);
-            const rows_f2 lhsA = h01a * h01a, rhsA = t2 * (h00a * hc);
-            const rows_f2 lhsB = h01b * h01b, rhsB = t2 * (h00bv * hc);
-            const rows_f2 loA = rhsA * (1.0f - beta), hiA = rhsA * (1.0f + beta);
-            const rows_f2 loB = rhsB * (1.0f - beta), hiB = rhsB * (1.0f + beta);
-            const bool ok0 = use_filter && (hc.x > 0.0f), ok1 = use_filter && (hc.y > 0.0f), okb = h00b > 0.0f;
+            // HET: the estimate of tanh(lth)^2 and the band of the header comment, per pair (both tests of a pair share them)
+            std::conditional_t<HET, rows_f2, float> t2x, bex;
+            [[maybe_unused]] rows_f2 ssum;  // the float sum of the pair's three sizes, in the order of ess_threshold_exact<1>
+            bool okn0 = true, okn1 = true;
+            if constexpr (HET)
+            {
+                const rows_f2 nav = {cur.na, cur.na}, nbv = {cur.nbu.x, cur.nbu.y};
+                ssum = (nav + nbv) + cur.nab;
+                const rows_f2 dm = ssum * 0.33333334f - 4.0f;
+                const rows_f2 u = {th2 * __builtin_amdgcn_rcpf(dm.x), th2 * __builtin_amdgcn_rcpf(dm.y)};
+                const rows_f2 pu = one + u * (-0.33333334f + u * (0.13333334f + u * (-0.053968254f + u * 0.021869488f)));
+                t2x = u * (pu * pu);
+                bex = rows_f2{kHetBeta0 + kHetBeta1 * __builtin_amdgcn_rsqf(t2x.x), kHetBeta0 + kHetBeta1 * __builtin_amdgcn_rsqf(t2x.y)};
+                // (every comparison is false for a NaN: sizes whose sum or estimate is not a number are "not sure")
+                okn0 = (dm.x >= kHetDMin) && (u.x >= kHetUMin) && (u.x <= kHetUMax);
+                okn1 = (dm.y >= kHetDMin) && (u.y >= kHetUMin) && (u.y <= kHetUMax);
+            }
+            else
+            {
+                t2x = t2;
+                bex = beta;
+            }
+            const rows_f2 lhsA = h01a * h01a, rhsA = t2x * (h00a * hc);
+            const rows_f2 lhsB = h01b * h01b, rhsB = t2x * (h00bv * hc);
+            const rows_f2 loA = rhsA * (1.0f - bex), hiA = rhsA * (1.0f + bex);
+            const rows_f2 loB = rhsB * (1.0f - bex), hiB = rhsB * (1.0f + bex);
+            const bool ok0 = use_filter && (hc.x > 0.0f) && okn0, ok1 = use_filter && (hc.y > 0.0f) && okn1, okb = h00b > 0.0f;
             bool passA0 = lhsA.x < loA.x, passA1 = lhsA.y < loA.y, passB0 = lhsB.x < loB.x, passB1 = lhsB.y < loB.y;
             const bool sureA0 = ok0 && (h00a.x > 0.0f) && (passA0 || lhsA.x > hiA.x);
             const bool sureA1 = ok1 && (h00a.y > 0.0f) && (passA1 || lhsA.y > hiA.y);
@@ -585,27 +711,42 @@ __global__ void __launch_bounds__(THREADS) level1_rows2_kernel(SweepParams p, Ro
             const bool slowA1 = needA1 && (VALIDATE || !sureA1), slowB1 = needB1 && (VALIDATE || !sureB1);
             if (__ballot(slowA0 || slowB0 || slowA1 || slowB1) != 0ull)
             {  // rare: the reference's operation order
+                // HET: the exact threshold of ess_threshold_exact<1> for the pair, lth = (float)((double)th / sqrt((double)me - 1 - 3))
+                // with me = s / 3 and s = (N[Y][X] + N[S][X]) + N[S][Y]: (X; ya | yb) sums (na + nb) + nab and (X; yb | ya)
+                // (nb + na) + nab, the same float, so one lth per pair serves both orientations.  A NaN size counts as 0
+                // (ess_term).  A negative radicand (mean size below 4) gives a NaN threshold exactly as on the exact sweep:
+                // z < NaN is false and the edge stays -- no special case.
+                [[maybe_unused]] float lth0 = th, lth1 = th;
+                if constexpr (HET)
+                {
+                    const float me0 = ssum.x / 3.0f, me1 = ssum.y / 3.0f;
+                    lth0 = (float)((double)th / sqrt((double)me0 - 1.0 - 3.0));
+                    lth1 = (float)((double)th / sqrt((double)me1 - 1.0 - 3.0));
+                }
+                if constexpr (HET)
+                    nslow += (needA0 && !sureA0 ? 1u : 0u) + (needB0 && !sureB0 ? 1u : 0u) + (needA1 && !sureA1 ? 1u : 0u) +
+                             (needB1 && !sureB1 ? 1u : 0u);
                 if (slowA0)
                 {
-                    const bool ex = level1_exact(h00a.x, h01a.x, hc.x, th);
+                    const bool ex = level1_exact(h00a.x, h01a.x, hc.x, HET ? lth0 : th);
                     if (VALIDATE && sureA0 && ex != passA0) viol++;
                     passA0 = ex;
                 }
                 if (slowB0)
                 {
-                    const bool ex = level1_exact(h00b, h01b.x, hc.x, th);
+                    const bool ex = level1_exact(h00b, h01b.x, hc.x, HET ? lth0 : th);
                     if (VALIDATE && sureB0 && ex != passB0) viol++;
                     passB0 = ex;
                 }
                 if (slowA1)
                 {
-                    const bool ex = level1_exact(h00a.y, h01a.y, hc.y, th);
+                    const bool ex = level1_exact(h00a.y, h01a.y, hc.y, HET ? lth1 : th);
                     if (VALIDATE && sureA1 && ex != passA1) viol++;
                     passA1 = ex;
                 }
                 if (slowB1)
                 {
-                    const bool ex = level1_exact(h00b, h01b.y, hc.y, th);
+                    const bool ex = level1_exact(h00b, h01b.y, hc.y, HET ? lth1 : th);
                     if (VALIDATE && sureB1 && ex != passB1) viol++;
                     passB1 = ex;
                 }
@@ -674,11 +815,14 @@ __global__ void __launch_bounds__(THREADS) level1_rows2_kernel(SweepParams p, Ro
     {
         ntests += __shfl_xor(ntests, o);  // < 2^32 per wave
         if (VALIDATE) viol += __shfl_xor(viol, o);
+        if constexpr (HET) nslow += __shfl_xor(nslow, o);
     }
     if (lane == 0)
     {
         if (ntests) atomicAdd(&s_cnt[0], (unsigned long long)ntests);
         if (VALIDATE && viol) atomicAdd(&s_cnt[1], (unsigned long long)viol);
+        if constexpr (HET)
+            if (nslow) atomicAdd(&s_cnt[2], (unsigned long long)nslow);
     }
     __syncthreads();
     if (tid == 0)
@@ -686,6 +830,10 @@ __global__ void __launch_bounds__(THREADS) level1_rows2_kernel(SweepParams p, Ro
         unsigned long long *sl = p.slots + (size_t)(blockIdx.x & (kCounterSlots - 1)) * 4;
         if (s_cnt[0]) atomicAdd(&sl[0], s_cnt[0]);
         if (s_cnt[1]) atomicAdd(&sl[3], s_cnt[1]);
+        // HET: the level has no recheck queue, its counter reports the tests that went to the exact form (rechecks[1]; the
+        // engine compares it with a queue capacity from level 2 on only)
+        if constexpr (HET)
+            if (s_cnt[2]) atomicAdd(&p.cnt->qcount, s_cnt[2]);
     }
 }
 
@@ -799,10 +947,12 @@ hipError_t launch_level1_apply(const SweepParams &p, const unsigned *sel, const 
 // Measured at n = 10,020, round 3 with three operand sets (gather form 0.336 ms): 256 threads (three rows per CU)
 // 0.255, 512 threads (two rows) 0.263, 384 threads (three rows, six waves each) 0.312, 1,024 threads (one row per
 // CU) 0.383; operand sets at 256 threads: 3: 0.254, 4: 0.244, 5: 0.242, 6: 0.243, 7: 0.246, 9 (two waves per SIMD): 0.328
-int level1_rows_threads(size_t row_lds, int mode, bool validate, int forced)
+// het: the HET forms carry the sizes as a further operand stream (VGPR counts in DESIGN section 9): 12 waves like the
+// validating forms, and row_lds holds two rows (C and N).
+int level1_rows_threads(size_t row_lds, int mode, bool validate, int forced, bool het)
 {
     constexpr size_t kLdsCu = 160 * 1024;
-    const int max_waves = (mode == 0 && !validate) ? 16 : 12;
+    const int max_waves = (mode == 0 && !validate && !het) ? 16 : 12;
     auto rows_per_cu = [&](int t) {
         const size_t fixed = sizeof(int4) * t + sizeof(int) * (2 * t + 1) + sizeof(int) * 2 * (t / 64) + 64;
         return std::min((int)(kLdsCu / (row_lds + fixed)), max_waves / (t / 64));
@@ -815,18 +965,22 @@ int level1_rows_threads(size_t row_lds, int mode, bool validate, int forced)
 
 extern "C" int cusk_level1_rows_threads(long long row_bytes, int mode, int validate, int forced_threads)
 {
-    if (row_bytes < 0 || (forced_threads != 0 && forced_threads != 256 && forced_threads != 512)) return -1;
-    return level1_rows_threads((size_t)row_bytes, mode, validate != 0, forced_threads);
+    if (row_bytes < 0 || mode < 0 || mode > 2 || (forced_threads != 0 && forced_threads != 256 && forced_threads != 512)) return -1;
+    // mode 2: Skeleton at per-pair sample sizes (the HET forms; row_bytes holds the rows of C and N)
+    return level1_rows_threads((size_t)row_bytes, mode == 2 ? 0 : mode, validate != 0, forced_threads, mode == 2);
 }
 
 hipError_t launch_level1_rows(int mode, bool validate, bool use_filter, const SweepParams &p, float *rv, void *meta,
                               unsigned *sel, const int *wpre, hipEvent_t ev_begin, hipEvent_t ev_end, int shard_rank,
                               int shard_world, int force_threads, bool lds_row, bool defer_apply, bool has_ti,
-                              unsigned long long *canon, hipStream_t st)
+                              unsigned long long *canon, hipStream_t st, float *nv, int *form)
 {
     const int n = p.n;
+    const bool het = nv != nullptr;  // per-pair sample sizes (p.Ness, bitwise symmetric): the HET forms, Skeleton mode only
+    if (het && (mode != 0 || p.Ness == nullptr)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(level1_prep_kernel, dim3((n + 3) / 4), dim3(256), 0, st, p.C, p.off, p.nbr, p.adj, wpre, p.words, rv,
                        static_cast<int4 *>(meta), sel, n, p.cnt);
+    if (het) hipLaunchKernelGGL(level1_prep_nv_kernel, dim3((n + 3) / 4), dim3(256), 0, st, p.Ness, p.off, p.nbr, nv, n, p.cnt);
     RowsParams rp;
     rp.rv = rv;
     rp.meta = static_cast<const int4 *>(meta);
@@ -836,36 +990,49 @@ hipError_t launch_level1_rows(int mode, bool validate, bool use_filter, const Sw
     rp.beta = level1_beta(p.t2);
     rp.shard_rank = shard_rank;
     rp.shard_world = shard_world;
+    rp.nv = nv;
+    rp.th2 = (float)((double)p.th * (double)p.th);
     const dim3 grid((unsigned)n);
     if (ev_begin) (void)hipEventRecord(ev_begin, st);
     // Row of C in LDS (4 (n + 8) bytes per workgroup) unless no row fits (level1_rows_threads), the matrix is not 16-byte
     // aligned or the caller asks for the gather form (option l1_lds_row = 0).
-    const size_t row_lds = sizeof(float) * ((size_t)(p.row_range ? p.max_span : n) + 8);
+    // HET: the row of N behind it, twice the bytes; N must be aligned as C is.
+    const size_t row_floats = (size_t)(p.row_range ? p.max_span : n) + 8;
+    const size_t nrow_off = (row_floats + 3) & ~(size_t)3;  // the row of N starts on a 16-byte boundary of LDS as well
+    const size_t row_lds = sizeof(float) * (het ? nrow_off + row_floats : row_floats);
+    rp.nrow_off = (int)nrow_off;
     int threads = 0;
-    if (lds_row && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0) threads = level1_rows_threads(row_lds, mode, validate, force_threads);
-#define CUSK_ROWS2_T(M, V, T)                                                                                     \
+    if (lds_row && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0 && (!het || (reinterpret_cast<uintptr_t>(p.Ness) & 15) == 0))
+        threads = level1_rows_threads(row_lds, mode, validate, force_threads, het);
+    if (form) *form = threads == 256 ? 2 : threads == 512 ? 3 : 4;
+#define CUSK_ROWS2_TH(M, V, T, H)                                                                                  \
     do                                                                                                            \
     {                                                                                                             \
         static size_t have = 0;                                                                                   \
         if (row_lds > have)                                                                                       \
         {                                                                                                         \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(level1_rows2_kernel<M, V, T, true>),         \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(level1_rows2_kernel<M, V, T, true, H>),         \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)row_lds);                  \
             have = row_lds;                                                                                       \
         }                                                                                                         \
-        hipLaunchKernelGGL((level1_rows2_kernel<M, V, T, true>), grid, dim3(T), row_lds, st, p, rp);              \
+        hipLaunchKernelGGL((level1_rows2_kernel<M, V, T, true, H>), grid, dim3(T), row_lds, st, p, rp);              \
     } while (0)
-#define CUSK_ROWS2(M, V)                                                                                          \
+#define CUSK_ROWS2(M, V) CUSK_ROWS2_H(M, V, false)
+#define CUSK_ROWS2_H(M, V, H)                                                                                     \
     do                                                                                                            \
     {                                                                                                             \
         if (threads == 256)                                                                                       \
-            CUSK_ROWS2_T(M, V, 256);                                                                              \
+            CUSK_ROWS2_TH(M, V, 256, H);                                                                           \
         else if (threads == 512)                                                                                  \
-            CUSK_ROWS2_T(M, V, 512);                                                                              \
+            CUSK_ROWS2_TH(M, V, 512, H);                                                                           \
         else                                                                                                      \
-            hipLaunchKernelGGL((level1_rows2_kernel<M, V, 256, false>), grid, dim3(256), 0, st, p, rp);           \
+            hipLaunchKernelGGL((level1_rows2_kernel<M, V, 256, false, H>), grid, dim3(256), 0, st, p, rp);         \
     } while (0)
-    if (mode == 0 && !validate)
+    if (het && !validate)
+        CUSK_ROWS2_H(0, false, true);
+    else if (het)
+        CUSK_ROWS2_H(0, true, true);
+    else if (mode == 0 && !validate)
         CUSK_ROWS2(0, false);
     else if (mode == 0)
         CUSK_ROWS2(0, true);
@@ -874,7 +1041,8 @@ hipError_t launch_level1_rows(int mode, bool validate, bool use_filter, const Sw
     else
         CUSK_ROWS2(1, true);
 #undef CUSK_ROWS2
-#undef CUSK_ROWS2_T
+#undef CUSK_ROWS2_H
+#undef CUSK_ROWS2_TH
     if (ev_end) (void)hipEventRecord(ev_end, st);
     if (mode != 0 && !defer_apply)
         hipLaunchKernelGGL(level1_apply_kernel, dim3((n + 3) / 4), dim3(256), 0, st, p.off, p.nbr, sel, p.adj, p.deg, n,

@@ -307,7 +307,9 @@ hipError_t launch_expand_records(const int *rec_s, const int *rec_l, long long r
 hipError_t launch_level1_rows(int mode, bool validate, bool use_filter, const SweepParams &p, float *rv, void *meta,
                               unsigned *sel, const int *wpre, hipEvent_t ev_begin, hipEvent_t ev_end, int shard_rank,
                               int shard_world, int force_threads, bool lds_row, bool defer_apply, bool has_ti,
-                              unsigned long long *canon, hipStream_t st);
+                              unsigned long long *canon, hipStream_t st, float *nv = nullptr, int *form = nullptr);
+// nv != nullptr: the HET forms at per-pair sample sizes (mode 0, p.Ness bitwise symmetric), nv = room for one float per CSR
+// slot (+ 4); form: which form was launched -- 2 / 3 row in LDS at 256 / 512 threads, 4 gather (cusk_engine_level1_form)
 // hetcor mode, row-sharded runs: adjacency bitmap -> per-slot marks (0 gone / all ones alive), and back after the join
 hipError_t launch_marks_from_bitmap(const SweepParams &p, unsigned *sel, hipStream_t st);
 hipError_t launch_level1_apply(const SweepParams &p, const unsigned *sel, const void *meta, bool count_removed, hipStream_t st);

@@ -86,6 +86,14 @@ class BlockSet:
             raise RuntimeError("cusk_blockset_set_het_filter failed")
         self.het_filter = bool(on)
 
+    def set_het_rows(self, on: bool = True) -> None:
+        """cusk_blockset_set_het_rows: the runs at per-pair sample sizes (run_block after set_het, run_batch_het) set engine
+        option het_rows on their engine -- level 1 of both stages on the row-streaming kernel at per-pair sample sizes
+        (`mps cusk ... het rows`); same files"""
+        if lib().cusk_blockset_set_het_rows(self.h, 1 if on else 0) != 0:
+            raise RuntimeError("cusk_blockset_set_het_rows failed")
+        self.het_rows = bool(on)
+
     def markers(self, i: int) -> int:
         return int(lib().cusk_blockset_block_markers(self.h, i))
 
@@ -484,7 +492,7 @@ def run_rank(bs, queue: _Queue, device: int, inflight: int = 1, options: dict | 
 def run_job(bs, outdir: str | None, device: int, inflight: int = 1, schedule: str = "lpt", collective_device=None,
             options: dict | None = None, group=None, engine_factory=None, store_key: str = "cusk_next_block",
             stage: bool = True, writer: str = "rank0", batch_vars: int = 0, timings: dict | None = None, blockfile: str | None = None,
-            het: bool = False, het_filter: bool = False):
+            het: bool = False, het_filter: bool = False, het_rows: bool = False):
     """One rank's part of the job (call on every rank of an initialised process group, or without one for a
     single-process run).  Returns (all results on rank 0 / None elsewhere, this rank's stats, assignment).
 
@@ -500,11 +508,14 @@ def run_job(bs, outdir: str | None, device: int, inflight: int = 1, schedule: st
 
     het (with batch_vars > 0): the batches run at per-pair sample sizes (cusk_blockset_run_batch_het).  Without batches the
     block set's own switch (BlockSet.set_het) decides, as before.  het_filter: the runs at per-pair sample sizes, batched
-    or block by block, go through the filter at levels >= 2 (BlockSet.set_het_filter); same files."""
+    or block by block, go through the filter at levels >= 2 (BlockSet.set_het_filter); same files.  het_rows: they run level 1
+    on the row-streaming kernel at per-pair sample sizes (BlockSet.set_het_rows); same files."""
     import torch.distributed as dist
 
     if het_filter:
         bs.set_het_filter(True)
+    if het_rows:
+        bs.set_het_rows(True)
 
     distributed = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if distributed else 0
@@ -630,6 +641,9 @@ def parse_args(argv=None):
     ap.add_argument("--het-filter", action="store_true",
                     help="with --het or --het-batch-vars: levels >= 2 of both stages through the filter and the recheck queue "
                          "instead of the exact path alone (`mps cusk ... het filter`); same files")
+    ap.add_argument("--het-rows", action="store_true",
+                    help="with --het or --het-batch-vars: level 1 of both stages on the row-streaming kernel at per-pair sample "
+                         "sizes instead of the exact sweep (`mps cusk ... het rows`); same files")
     ap.add_argument("--no-stage", action="store_true", help="do not keep the whole .bed in HBM; every block uploads its slice")
     ap.add_argument("--device", type=int, default=None, help="GPU of this rank (default LOCAL_RANK modulo the device count)")
     args = ap.parse_args(argv)
@@ -643,6 +657,8 @@ def parse_args(argv=None):
         ap.error("--het runs one block per engine run: it cannot be combined with a non-zero --batch-vars")
     if args.het_filter and not args.het:
         ap.error("--het-filter applies to runs at per-pair sample sizes: give --het or --het-batch-vars with it")
+    if args.het_rows and not args.het:
+        ap.error("--het-rows applies to runs at per-pair sample sizes: give --het or --het-batch-vars with it")
     if args.batch_vars is None:
         args.batch_vars = 0 if args.het else 16384
     return args
@@ -682,7 +698,7 @@ def main(argv=None):
     writer = args.writer if (batch_vars > 0 or args.writer != "merge") else "rank0"  # (merge is part of the batched path)
     allr, stats, owned = run_job(bs, args.outdir, device, args.inflight, args.schedule, cdev, stage=not args.no_stage,
                                  options={"timing": 0}, writer=writer, batch_vars=batch_vars, blockfile=args.blocks, het=het_batch,
-                                 het_filter=args.het_filter)
+                                 het_filter=args.het_filter, het_rows=args.het_rows)
     dt = time.perf_counter() - t0
     if batch_vars > 0:
         tests = sum(int(s.tests[0]) + int(s.tests[1]) for s in stats)
@@ -692,6 +708,16 @@ def main(argv=None):
         nblk, nskip = len(stats), sum(1 for s in stats.values() if s.skipped)
     print(f"[rank {rank}/{world}] gpu {device}: {nblk} blocks ({nskip} skipped), "
           f"{tests:.3e} CI tests, open {t_open:.2f} s, total {dt:.2f} s", flush=True)
+    if args.het_rows:
+        # a level 1 that ran on the row kernel forms no conditioning sets (subsets[1] = 0 beside tests[1] > 0); rechecks[1]
+        # counts the tests its filter sent to the exact form
+        runs = list(stats) if batch_vars > 0 else list(stats.values())
+        on = [sum(1 for s in runs if s.stage[k].tests[1] > 0 and s.stage[k].subsets[1] == 0) for k in range(2)]
+        ran = [sum(1 for s in runs if s.stage[k].tests[1] > 0) for k in range(2)]
+        sent = sum(int(s.stage[k].rechecks[1]) for s in runs for k in range(2))
+        l1 = sum(int(s.stage[k].tests[1]) for s in runs for k in range(2))
+        print(f"[rank {rank}] het rows: level 1 on the row kernel in {on[0]} of {ran[0]} stage-one and {on[1]} of {ran[1]} "
+              f"stage-two runs, {sent} of {l1} level-1 tests sent to the exact form", flush=True)
     if rank == 0 or writer in ("local", "merge"):
         print(f"[rank {rank}] wrote {len(allr)} of {bs.num_blocks} blocks to {args.outdir}"
               + (" + merged_blocks*" if (writer == "merge" and rank == 0) else ""), flush=True)

@@ -222,6 +222,11 @@ class Engine:
     def set_option(self, key: str, value: int) -> None:
         self._check(lib().cusk_engine_set_option(self.h, key.encode(), int(value)))
 
+    def level1_form(self) -> int:
+        """cusk_engine_level1_form: the kernel that ran level 1 in the last run -- 0 generic sweep, 1 pair kernel, 2 / 3 row
+        kernel with the row in LDS at 256 / 512 threads, 4 row kernel in its gather form, -1 no level 1 ran"""
+        return int(lib().cusk_engine_level1_form(self.h))
+
     def set_row_shard(self, rank: int, world: int, exchange=None, host_staging: bool = True) -> None:
         """Row-sharded sweep of one block over `world` engines (cusk_engine_set_row_shard).  `exchange(level, buf,
         count, elem_bytes, on_device, stream) -> int` must all-reduce the buffer with an element-wise unsigned MIN

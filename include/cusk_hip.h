@@ -99,7 +99,9 @@ typedef struct cusk_stats {
     float kernel_ms[CUSK_ML + 1];     /* HIP-event time of the level's sweep kernels */
     float level_ms[CUSK_ML + 1];      /* HIP-event time of the whole level (compaction + sweep + finalise) */
     float total_ms;                   /* whole run, events on the engine stream */
-    long long rechecks[CUSK_ML + 1];  /* tests the fast filter could not certify (re-evaluated on the exact path) */
+    long long rechecks[CUSK_ML + 1];  /* tests the fast filter could not certify (re-evaluated on the exact path); level 1: 0,
+                                         except with option "het_rows", where it counts the tests the row kernel's
+                                         filter sent to the exact form (and subsets[1] is 0 as for every row-kernel run) */
     long long violations;             /* validate mode only: certified verdicts contradicted by the exact path */
     long long exact_fallbacks;        /* levels redone entirely on the exact path (recheck queue overflow) */
     float main_kernel_ms[CUSK_ML + 1]; /* HIP-event time of the level's dominant kernel alone (level 1: the rows
@@ -128,13 +130,15 @@ const char *cusk_last_error(const cusk_engine *e);
  * cusk_corr_build on the FP4 matrix pipe; 0: the int8 MFMA form), "corr_popcount" (default 0; 1: bit-plane AND/popcount
  * cross-check kernels instead of the matrix cores), "corr_mxp_f32" (default 0: SNP x trait sums on the bf16 matrix pipe with every
  * trait value split exactly into three bf16 pieces; 1: the f32 matrix instructions of rounds 1-2), "assume_symmetric" (default 0: level 0 verifies C == C^T bitwise;
- * 1: the caller guarantees it, e.g. a matrix written by cusk_corr_build), "queue_capacity" (recheck queue entries, default 4Mi), "chunk" (combination ranks per work item, default 2048), "timing" (HIP events for cusk_stats: 0 total_ms only; 1, the default, around every level's sweep: kernel_ms, and level_ms = end of the previous level's sweep to the end of this one's; 2 also level start / end: level_ms = plan to finaliser; 3 only the pair around the level-1 row kernel: main_kernel_ms[1] -- every event costs a few microseconds of device time), "chunk0" (conditioning sets per work item of the first degree class, default 512), "tmaj_min_level" (first level swept by unions T = S + Y, one inverse per l + 1 tests: default 6, 99 = never; single threshold and symmetric matrix only), "tmaj_validate_stride" (with "validate": the union-major sweep checks the unions whose per-lane count is a multiple of this power of two against double precision; default 1 = all), "hostprof" (1: host-side phase marks of every run on stderr), "max_staged_classes" (test hook: at most this many degree classes keep their sub-matrix in LDS; 0 sends every row through the kernels of the unstaged class), "chunk0_low" (work-item size of the first degree class at levels 2-4, default 256), "vec_threads" (workgroup size of the vectorised sweep for the first degree class: 64, 128 or 256; default 64), "lookahead" (levels the host enqueues ahead of the level counters it has seen, default 2; every kernel checks its level's gate on the device), "sync2" (default 1: the host reads level 2's gate record -- class counts, maximum degree -- before it enqueues that level's sweeps, so that degree classes that turn out empty are not launched at levels >= 2; 0: enqueue ahead on the level-1 degree bound), "item_capacity" (work items per degree class and level the buffers hold before the engine grows them and takes the level up again, default 1Mi), "het_filter" (default 0: cusk_run_skeleton_het / cusk_run_skeleton_batch_het run every level on the exact path; 1: their levels >= 2 go through the filter at the per-test threshold and the recheck queue like the other modes, "fast" = 0 still selects the exact path, and "validate" is accepted), "sepselect_ws_bytes" (HBM work space of
+ * 1: the caller guarantees it, e.g. a matrix written by cusk_corr_build), "queue_capacity" (recheck queue entries, default 4Mi), "chunk" (combination ranks per work item, default 2048), "timing" (HIP events for cusk_stats: 0 total_ms only; 1, the default, around every level's sweep: kernel_ms, and level_ms = end of the previous level's sweep to the end of this one's; 2 also level start / end: level_ms = plan to finaliser; 3 only the pair around the level-1 row kernel: main_kernel_ms[1] -- every event costs a few microseconds of device time), "chunk0" (conditioning sets per work item of the first degree class, default 512), "tmaj_min_level" (first level swept by unions T = S + Y, one inverse per l + 1 tests: default 6, 99 = never; single threshold and symmetric matrix only), "tmaj_validate_stride" (with "validate": the union-major sweep checks the unions whose per-lane count is a multiple of this power of two against double precision; default 1 = all), "hostprof" (1: host-side phase marks of every run on stderr), "max_staged_classes" (test hook: at most this many degree classes keep their sub-matrix in LDS; 0 sends every row through the kernels of the unstaged class), "chunk0_low" (work-item size of the first degree class at levels 2-4, default 256), "vec_threads" (workgroup size of the vectorised sweep for the first degree class: 64, 128 or 256; default 64), "lookahead" (levels the host enqueues ahead of the level counters it has seen, default 2; every kernel checks its level's gate on the device), "sync2" (default 1: the host reads level 2's gate record -- class counts, maximum degree -- before it enqueues that level's sweeps, so that degree classes that turn out empty are not launched at levels >= 2; 0: enqueue ahead on the level-1 degree bound), "item_capacity" (work items per degree class and level the buffers hold before the engine grows them and takes the level up again, default 1Mi), "het_filter" (default 0: cusk_run_skeleton_het / cusk_run_skeleton_batch_het run every level on the exact path; 1: their levels >= 2 go through the filter at the per-test threshold and the recheck queue like the other modes, "fast" = 0 still selects the exact path, and "validate" is accepted), "het_rows" (0 or 1, default 0: level 1 of cusk_run_skeleton_het / cusk_run_skeleton_batch_het runs on the exact sweep; 1: on the row-streaming level-1 kernel at per-pair sample sizes when "fast", "pair" and "rows" are non-zero and both C and N_dev are symmetric, N_dev bit for bit -- otherwise as with 0; same results; cusk_engine_level1_form tells which kernel ran), "sepselect_ws_bytes" (HBM work space of
  * cusk_sepselect_greedy for candidate lists too long for LDS, default 4 GiB; such pairs run in batches of what fits). */
 int cusk_engine_set_option(cusk_engine *e, const char *key, long long value);
 /* Host only, no device needed: the workgroup size level 1's row-streaming kernel runs with when a row of C takes
  * row_bytes of LDS (4 (n + 8) for a single n x n matrix), or 0 when it gathers the row through the caches instead.
  * mode 0 Skeleton / 1 hetcor; forced_threads as the test options "l1_threads" (0 / 256 / 512; "l1_lds_row" = 0 and a
- * matrix that is not 16-byte aligned always give the gather form).  -1 for arguments out of range. */
+ * matrix that is not 16-byte aligned always give the gather form).  -1 for arguments out of range.  mode 2: the
+ * forms at per-pair sample sizes (Skeleton mode with option "het_rows"), which keep the row of N behind the row of C:
+ * row_bytes = 2 * 4 (n + 8), rounded up by at most 12 bytes so that the second row starts on a 16-byte boundary. */
 int cusk_level1_rows_threads(long long row_bytes, int mode, int validate, int forced_threads);
 void *cusk_engine_stream(const cusk_engine *e);
 /* Makes the engine's device the calling thread's current HIP device, so that the cusk_dev_* helpers below act on it.
@@ -196,6 +200,11 @@ int cusk_run_hetcor(cusk_engine *e, const float *C_dev, const float *N_dev, floa
  * records and pMax are those of the exact path either way. */
 int cusk_run_skeleton_het(cusk_engine *e, const float *C_dev, const float *N_dev, int n, float th, int maxlevel,
                           cusk_stats *stats);
+/* Which kernel ran level 1 in the engine's last run (any mode): 0 the generic sweep, 1 the pair kernel, 2 / 3 the
+ * row-streaming kernel with the row in LDS at 256 / 512 threads, 4 the row-streaming kernel in its gather form, -1 no level 1
+ * ran (or no run yet).  With option "het_rows" it tells a row-kernel run at per-pair sample sizes from the fall-back to the
+ * exact sweep (asymmetric N_dev or C, "fast" / "pair" / "rows" = 0). */
+int cusk_engine_level1_form(const cusk_engine *e);
 
 /* Batched Skeleton run: `nblk` independent blocks (the LD blocks of one GPU's share of a chromosome job, or their reduced
  * stage-two sets) swept in ONE run.  The reference has no counterpart: it runs one block per process (src/cli.cpp:507-512,
@@ -494,6 +503,10 @@ int cusk_blockset_set_het(cusk_blockset *bs, int het);
  * cusk_blockset_run_batch_het) set engine option "het_filter" = 1 on the engine they are given, for both stages
  * (`mps cusk ... het filter`).  Same files; 0 (default) leaves the engine's option as it is.  Set it before running blocks. */
 int cusk_blockset_set_het_filter(cusk_blockset *bs, int on);
+/* on = 1: the same runs set engine option "het_rows" = 1 on the engine they are given, for both stages (`mps cusk ... het
+ * rows`): level 1 on the row-streaming kernel at per-pair sample sizes.  Same files; 0 (default) leaves the engine's option
+ * as it is.  Set it before running blocks. */
+int cusk_blockset_set_het_rows(cusk_blockset *bs, int on);
 /* Forgets what the block set keeps for engine e -- its device scratch (block matrices) and the state of a correlation
  * build started ahead -- and releases that memory.  Call before destroying an engine that ran blocks of this set when the
  * set outlives it (cusk_blockset_close releases everything anyway). */
