@@ -124,6 +124,8 @@ SYMBOLS = {
     "cusk_pair_counts": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),
     "cusk_ess_square": (_i, [_vp, _vp, _vp, _sz, _sz, _f, _vp]),
     "cusk_ess_square_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _sz, _f, _i, _vp]),
+    "cusk_marker_pair_sizes": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz]),
+    "cusk_marker_pair_sizes_batch": (_i, [_vp, _vp, _vp, _sz, _sz, _i, _vp, _vp, _i, _vp]),
     "cusk_ess_from_se": (_f, [_f, _f]),
     "cusk_se_from_count": (_f, [_f, _i]),
     "cusk_sumstats_write_se": (_i, [C.c_char_p, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, C.c_char_p, _sz]),
@@ -148,6 +150,7 @@ SYMBOLS = {
     "cusk_blockset_set_het": (_i, [_vp, _i]),
     "cusk_blockset_set_het_filter": (_i, [_vp, _i]),
     "cusk_blockset_set_het_rows": (_i, [_vp, _i]),
+    "cusk_blockset_set_het_markers": (_i, [_vp, _i]),
     "cusk_blockset_release_engine": (None, [_vp, _vp]),
     "cusk_blockset_run_batch": (_i, [_vp, _vp, _vp, _i, C.POINTER(_vp), _vp]),
     "cusk_blockset_run_batch_het": (_i, [_vp, _vp, _vp, _i, C.POINTER(_vp), _vp]),

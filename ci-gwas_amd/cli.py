@@ -73,6 +73,10 @@ def _add_cusk(sub):
     p.add_argument("--het-rows", action="store_true",
                    help="with --het: level 1 of both stages on the row-streaming kernel at per-pair sample sizes instead of the "
                         "exact sweep (`mps cusk ... het rows`); same output files")
+    p.add_argument("--het-markers", action="store_true",
+                   help="with --het: every pair of markers is tested at the number of individuals both were genotyped on "
+                        "(.bed code 01 = missing) instead of all of them (`mps cusk ... het markers`); the output changes where "
+                        "markers have missing calls")
     p.set_defaults(func=cusk)
 
 
@@ -124,6 +128,9 @@ def _add_cuskss(sub, name, help_):
         p.add_argument("--het", action="store_true",
                        help="with --bfiles: per-pair sample sizes (the individuals both variables were observed on) instead "
                             "of the number of individuals; the result of --mxp-se/--pxp-se on the files of `sumstats --se`")
+        p.add_argument("--het-markers", action="store_true",
+                       help="with --bfiles and --het: also every pair of markers at the number of individuals both were "
+                            "genotyped on instead of the number of individuals (`mps cuskss-bed ... het markers`)")
     p.set_defaults(func=cuskss, variant=name)
 
 
@@ -206,10 +213,13 @@ def cusk_argv(args) -> list[str]:
         sys.exit("cusk: --het-filter applies to runs at per-pair sample sizes: give --het with it.")
     if getattr(args, "het_rows", False) and not getattr(args, "het", False):
         sys.exit("cusk: --het-rows applies to runs at per-pair sample sizes: give --het with it.")
+    if getattr(args, "het_markers", False) and not getattr(args, "het", False):
+        sys.exit("cusk: --het-markers applies to runs at per-pair sample sizes: give --het with it.")
     return [MPS_PATH, "cusk", args.phen, args.bfiles, args.blocks, str(args.alpha), str(args.max_level),
             str(args.max_level_two), str(args.max_depth), args.outdir, str(args.block_index)] + (
                 ["het"] if getattr(args, "het", False) else []) + (["filter"] if getattr(args, "het_filter", False) else []) + (
-                    ["rows"] if getattr(args, "het_rows", False) else [])
+                    ["rows"] if getattr(args, "het_rows", False) else []) + (
+                        ["markers"] if getattr(args, "het_markers", False) else [])
 
 
 def sumstats_argv(args) -> list[str]:
@@ -226,6 +236,8 @@ def cuskss_bed_argv(args) -> list[str]:
     what `sumstats` writes"""
     if args.bfiles is None or args.phen is None:
         sys.exit("cuskss-merged: --bfiles and --phen go together.")
+    if getattr(args, "het_markers", False) and not args.het:
+        sys.exit("cuskss-merged: --het-markers applies to runs at per-pair sample sizes: give --het with it.")
     if any(v != "NULL" for v in (args.mxm, args.mxp, args.pxp)):
         sys.exit("cuskss-merged: give either --bfiles/--phen or --mxm/--mxp/--pxp, not both.")
     if args.mxp_se != "NULL" or args.pxp_se != "NULL":
@@ -245,7 +257,8 @@ def cuskss_bed_argv(args) -> list[str]:
             sys.exit(f"cuskss-merged: --num-samples {args.num_samples} differs from the {in_dim} individuals of "
                      f"{args.bfiles}.dim.")
     return [MPS_PATH, "cuskss-bed", args.phen, args.bfiles, args.marker_indices, args.time_index, str(args.alpha),
-            str(args.max_level_one), str(args.max_level_two), str(args.max_depth), args.outdir] + (["het"] if args.het else [])
+            str(args.max_level_one), str(args.max_level_two), str(args.max_depth), args.outdir] + (["het"] if args.het else []) + (
+                ["markers"] if getattr(args, "het_markers", False) else [])
 
 
 def cuskss_argv(args) -> list[str]:
@@ -254,6 +267,8 @@ def cuskss_argv(args) -> list[str]:
         return cuskss_bed_argv(args)
     if getattr(args, "het", False):
         sys.exit("cuskss-merged: --het needs --bfiles and --phen (with correlation files, give --mxp-se/--pxp-se).")
+    if getattr(args, "het_markers", False):
+        sys.exit("cuskss-merged: --het-markers needs --bfiles, --phen and --het (correlation files carry no marker x marker sizes).")
     if args.pxp == "NULL":
         sys.exit("the following arguments are required: --pxp")
     if args.num_samples is None:

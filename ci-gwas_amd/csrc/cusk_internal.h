@@ -171,6 +171,7 @@ struct cusk_engine
     // correlation build scratch
     cusk::DevBuf bed_dev, phen_dev, mean_dev, std_dev, planes, mxp_dev, pxp_dev, mxp_bq;
     cusk::DevBuf pc_masks, pc_counts;  // cusk_pair_counts: trait masks in the .bed bit layout, the counts before their download
+    cusk::DevBuf mp_bits;              // cusk_marker_pair_sizes: one validity bit per marker and individual, rows padded to whole slabs
     cusk::DevBuf corr_tab[2];  // batched build: block / tile tables of phase one (marker x trait) and two (marker x marker)
     void *corr_tab_pinned[2] = {nullptr, nullptr};
     size_t corr_tab_pinned_cap[2] = {0, 0};

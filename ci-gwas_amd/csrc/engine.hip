@@ -926,7 +926,7 @@ extern "C" void cusk_engine_destroy(cusk_engine *e)
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->stream2) (void)hipStreamSynchronize(e->stream2);
     if (e->stream3) (void)hipStreamSynchronize(e->stream3);
-    for (DevBuf *b : {&e->row_range, &e->row_blk, &e->blk_woff, &e->pxp_dev, &e->corr_tab[0], &e->corr_tab[1], &e->pc_masks, &e->pc_counts})
+    for (DevBuf *b : {&e->row_range, &e->row_blk, &e->blk_woff, &e->pxp_dev, &e->corr_tab[0], &e->corr_tab[1], &e->pc_masks, &e->pc_counts, &e->mp_bits})
         b->release();
     if (e->res_pinned) (void)hipHostFree(e->res_pinned);
     for (void *ph : e->corr_tab_pinned)

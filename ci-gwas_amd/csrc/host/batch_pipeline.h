@@ -275,6 +275,18 @@ inline void run_cusk_batch(cusk_engine *e, const CuskInputs &in, const StagedInp
         scr.Ness.reserve(n1 * n1);
         if (cusk_ess_square_batch(e, me.data(), pe.data(), K, mk.data(), lo1.data(), p, (float)N, (int)n1, scr.Ness.p) != CUSK_OK)
             engine_die("sample-size matrix (batch)", e);
+        if (in.het_markers)
+        {  // the kept blocks' rows in one list, block after block (a block named twice repeats its rows)
+            std::vector<int> rows;
+            for (int k = 0; k < K; k++)
+            {
+                const size_t b = (size_t)kept[(size_t)k];
+                for (int i = 0; i < m[b]; i++) rows.push_back((int)(first[b] + i));
+            }
+            if (cusk_marker_pair_sizes_batch(e, staged.bed, rows.data(), (in.bed.size - 3) / bpc, N, K, mk.data(), lo1.data(), (int)n1,
+                                             scr.Ness.p) != CUSK_OK)
+                engine_die("marker pair sizes (batch)", e);
+        }
         mark("ess_square");
         bs.ms_corr += ms_since(t);
         if (in.het_filter) cusk_engine_set_option(e, "het_filter", 1);  // (stays set for stage two)

@@ -226,6 +226,18 @@ extern "C" int cusk_blockset_set_het_rows(cusk_blockset *bs, int on)
     return CUSK_OK;
 }
 
+extern "C" int cusk_blockset_set_het_markers(cusk_blockset *bs, int on)
+{
+    if (!bs) return CUSK_ERR_ARG;
+    if (on != 0 && !bs->in.het)
+    {
+        copy_err("cusk_blockset_set_het_markers: the set does not run at per-pair sample sizes (cusk_blockset_set_het first)", nullptr, 0);
+        return CUSK_ERR_ARG;
+    }
+    bs->in.het_markers = on != 0;
+    return CUSK_OK;
+}
+
 extern "C" void cusk_blockset_release_engine(cusk_blockset *bs, cusk_engine *e)
 {
     if (!bs || !e) return;

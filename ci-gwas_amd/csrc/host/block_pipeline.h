@@ -464,6 +464,9 @@ struct CuskInputs
     // `mps cusk ... het rows`: the het runs set engine option het_rows (level 1 on the row kernel at per-pair sample sizes
     // when the size matrix is symmetric); same results
     bool het_rows = false;
+    // `mps cusk ... het markers`: a pair of markers is tested at the number of individuals both were observed on
+    // (cusk_marker_pair_sizes over the marker x marker part of the size matrix) instead of N; results change
+    bool het_markers = false;
     MappedFile bed;
     // all markers' means / stds, read once when several blocks are run from one process (empty: line-range reads)
     std::vector<float> means_all, stds_all;
@@ -499,8 +502,8 @@ struct CuskInputs
     size_t first_marker(const Block &b) const { return bim.start_of(b.chr) + b.first; }
 };
 
-// argv of `mps cusk` (cli.cpp:432-456 plus the optional trailing `het`, which the words `filter` and `rows` may follow in
-// either order, each at most once): false = too few arguments (the caller prints the usage text and exits with 1); an
+// argv of `mps cusk` (cli.cpp:432-456 plus the optional trailing `het`, which the words `filter`, `rows` and `markers` may
+// follow in any order, each at most once): false = too few arguments (the caller prints the usage text and exits with 1); an
 // unknown or repeated trailing argument, or one too many, dies with a message (status 1)
 inline bool parse_cusk_args(int argc, char **argv, CuskInputs &in, std::string &outdir, int &block_index)
 {
@@ -516,7 +519,7 @@ inline bool parse_cusk_args(int argc, char **argv, CuskInputs &in, std::string &
     block_index = std::stoi(argv[10]);
     in.het = argc > 11;
     if (in.het && std::string(argv[11]) != "het") die(std::string("cusk: unknown trailing argument ") + argv[11]);
-    in.het_filter = in.het_rows = false;
+    in.het_filter = in.het_rows = in.het_markers = false;
     for (int i = 12; i < argc; i++)
     {
         const std::string w(argv[i]);
@@ -524,6 +527,8 @@ inline bool parse_cusk_args(int argc, char **argv, CuskInputs &in, std::string &
             in.het_filter = true;
         else if (w == "rows" && !in.het_rows)
             in.het_rows = true;
+        else if (w == "markers" && !in.het_markers)
+            in.het_markers = true;
         else
             die(std::string("cusk: unknown trailing argument ") + argv[i]);
     }
@@ -690,6 +695,9 @@ inline bool run_cusk_block(cusk_engine *e, const CuskInputs &in, int block_index
         block_sample_sizes(mxp.data(), mxp_n.data(), pxp.data(), pxp_n.data(), m, p, mxp_ess, pxp_ess);
         scr.Ness.reserve(n * n);
         if (cusk_ess_square(e, mxp_ess.data(), pxp_ess.data(), m, p, (float)N, scr.Ness.p) != CUSK_OK) engine_die("sample-size matrix", e);
+        // (het markers) the block's own rows once more: jointly observed individuals per pair of markers over the m x m corner
+        if (in.het_markers && cusk_marker_pair_sizes(e, bed, nullptr, m, m, N, scr.Ness.p, n) != CUSK_OK)
+            engine_die("marker pair sizes", e);
         bs.ms_ess = ms_since(t);
         bs.ms_corr += bs.ms_counts + bs.ms_ess;
     }

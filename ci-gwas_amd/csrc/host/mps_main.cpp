@@ -3,7 +3,7 @@
 // Same positional argv contracts, stdout milestones, exit codes and output files as the
 // reference's native CLI (/root/reference/cusk/apps/mps.cpp:17-121, src/cli.cpp:194-346,
 // :432-678), so that ci-gwas.py (or this repo's cli shim) can call it unchanged:
-//   mps cusk   <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het] [filter] [rows]
+//   mps cusk   <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het] [filter] [rows] [markers]
 //   mps cuskss <mxm> <mxp> <mxp_se> <pxp> <pxp_se> <time_index> <block_index> <blockfile>
 //              <marker_indices> <alpha> <l1> <l2> <depth> <num_samples> <outdir>   ("NULL" = absent)
 // and two commands the reference does not have, for users who hold the genotypes (see SUMSTATS_USAGE):
@@ -35,7 +35,7 @@ namespace {
 const char *CUSK_USAGE = R"(
 Run the skeleton search on a single block of a block diagonal genomic covariance matrix.
 
-usage: mps cusk <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het] [filter] [rows]
+usage: mps cusk <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het] [filter] [rows] [markers]
 
 arguments:
     het             test every marker-trait and trait-trait pair at the number of individuals it was observed on (.phen
@@ -45,6 +45,9 @@ arguments:
                     path alone (engine option het_filter).  Same five output files.
     rows            (after het, before or after filter) level 1 of both stages on the row-streaming kernel at per-pair
                     sample sizes (engine option het_rows).  Same five output files.
+    markers         (after het, in any order with filter and rows) test every pair of markers at the number of individuals
+                    both were genotyped on (.bed code 01 = missing) instead of all of them.  The files change where
+                    markers have missing calls.
 )";
 
 // wall-clock phase marks, printed as "[t] <phase>: <ms> ms" when CUSK_TIMING is set (tools/e2e_block.py)
@@ -76,7 +79,8 @@ int cmd_cusk(int argc, char **argv)
               << "\nalpha: " << in.alpha << "\nmax_level: " << in.max_level << "\nmax_level_two: " << in.max_level_two
               << "\ndepth: " << in.depth << "\noutdir: " << outdir << "\nblock-index: " << block_index << std::endl;
     if (in.het) std::cout << "het: per-pair sample sizes" << (in.het_filter ? ", levels >= 2 through the filter" : "")
-                          << (in.het_rows ? ", level 1 on the row kernel" : "") << std::endl;
+                          << (in.het_rows ? ", level 1 on the row kernel" : "") << (in.het_markers ? ", marker pairs at their own counts" : "")
+                          << std::endl;
 
     PhaseTimer tm;
     check_path(outdir);
@@ -339,10 +343,12 @@ arguments:
 const char *CUSKSS_BED_USAGE = R"(
 Run cuskss on the markers selected in all blocks, with the correlations computed from genotypes on the device.
 
-usage: mps cuskss-bed <.phen> <bfiles> <marker-indices> <time_index|NULL> <alpha> <max_level_one> <max_level_two> <depth> <outdir> [het]
+usage: mps cuskss-bed <.phen> <bfiles> <marker-indices> <time_index|NULL> <alpha> <max_level_one> <max_level_two> <depth> <outdir> [het] [markers]
 
     het             test every marker-trait and trait-trait pair at the number of individuals it was observed on (.phen
                     with NA) instead of all of them: the result of cuskss on the files of `mps sumstats ... se`
+    markers         (after het) also every pair of markers at the number of individuals both were genotyped on (.bed code
+                    01 = missing) instead of all of them; cuskss_merged.ess carries those counts in its marker x marker part
 )";
 
 // .phen, the prep files and the marker selection; the arrays every kernel reads are copied to the device once
@@ -558,6 +564,9 @@ int cmd_cuskss_bed(int argc, char **argv)
     const std::string outdir = argv[10];
     const bool het = argc > 11;
     if (het && std::string(argv[11]) != "het") die(std::string("cuskss-bed: unknown trailing argument ") + argv[11]);
+    const bool het_markers = argc > 12;
+    if (het_markers && std::string(argv[12]) != "markers") die(std::string("cuskss-bed: unknown trailing argument ") + argv[12]);
+    if (argc > 13) die(std::string("cuskss-bed: unknown trailing argument ") + argv[13]);
     if (index_path == "NULL") die("cuskss-bed needs marker indices");
     check_path(outdir);
     const bool time_indexed = time_index_path != "NULL";
@@ -607,6 +616,15 @@ int cmd_cuskss_bed(int argc, char **argv)
             const float nan = std::numeric_limits<float>::quiet_NaN();
             auto ess_of = [&](float r, int count) { return std::isnan(r) ? nan : cusk_ess_from_se(r, cusk_se_from_count(r, count)); };
             gc.ess.assign(n * n, num_samples);
+            if (het_markers)
+            {  // between markers: the individuals both were genotyped on, counted on the device into a k x k scratch
+                DevMat Nmm(k * k);
+                std::vector<float> cnt(k * k);
+                if (cusk_marker_pair_sizes(e, in.bed_rows(), in.ixs.data(), k, in.m(), in.N(), Nmm.p, k) != CUSK_OK)
+                    engine_die("marker pair sizes", e);
+                if (cusk_dev_download(cnt.data(), Nmm.p, sizeof(float) * k * k) != CUSK_OK) engine_die("marker pair sizes (download)", e);
+                for (size_t i = 0; i < k; i++) std::copy_n(&cnt[i * k], k, &gc.ess[i * n]);
+            }
             for (size_t i = 0; i < k; i++)
                 for (size_t t = 0; t < p; t++)
                     gc.ess[i * n + k + t] = gc.ess[(k + t) * n + i] = ess_of(mxp[i * p + t], mxp_n[i * p + t]);

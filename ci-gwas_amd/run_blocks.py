@@ -94,6 +94,14 @@ class BlockSet:
             raise RuntimeError("cusk_blockset_set_het_rows failed")
         self.het_rows = bool(on)
 
+    def set_het_markers(self, on: bool = True) -> None:
+        """cusk_blockset_set_het_markers: the runs at per-pair sample sizes give every pair of markers of a block the number of
+        individuals both were genotyped on instead of the number of individuals (`mps cusk ... het markers`); results
+        change where markers have missing calls.  Switching it on is an error unless set_het(True) came first"""
+        if lib().cusk_blockset_set_het_markers(self.h, 1 if on else 0) != 0:
+            raise RuntimeError("cusk_blockset_set_het_markers failed: " + (lib().cusk_blockset_last_error() or b"").decode())
+        self.het_markers = bool(on)
+
     def markers(self, i: int) -> int:
         return int(lib().cusk_blockset_block_markers(self.h, i))
 
@@ -492,7 +500,7 @@ def run_rank(bs, queue: _Queue, device: int, inflight: int = 1, options: dict | 
 def run_job(bs, outdir: str | None, device: int, inflight: int = 1, schedule: str = "lpt", collective_device=None,
             options: dict | None = None, group=None, engine_factory=None, store_key: str = "cusk_next_block",
             stage: bool = True, writer: str = "rank0", batch_vars: int = 0, timings: dict | None = None, blockfile: str | None = None,
-            het: bool = False, het_filter: bool = False, het_rows: bool = False):
+            het: bool = False, het_filter: bool = False, het_rows: bool = False, het_markers: bool = False):
     """One rank's part of the job (call on every rank of an initialised process group, or without one for a
     single-process run).  Returns (all results on rank 0 / None elsewhere, this rank's stats, assignment).
 
@@ -509,13 +517,17 @@ def run_job(bs, outdir: str | None, device: int, inflight: int = 1, schedule: st
     het (with batch_vars > 0): the batches run at per-pair sample sizes (cusk_blockset_run_batch_het).  Without batches the
     block set's own switch (BlockSet.set_het) decides, as before.  het_filter: the runs at per-pair sample sizes, batched
     or block by block, go through the filter at levels >= 2 (BlockSet.set_het_filter); same files.  het_rows: they run level 1
-    on the row-streaming kernel at per-pair sample sizes (BlockSet.set_het_rows); same files."""
+    on the row-streaming kernel at per-pair sample sizes (BlockSet.set_het_rows); same files.  het_markers: they test pairs of
+    markers at the number of individuals both were genotyped on (BlockSet.set_het_markers, which wants BlockSet.set_het(True)
+    first); the files change where markers have missing calls."""
     import torch.distributed as dist
 
     if het_filter:
         bs.set_het_filter(True)
     if het_rows:
         bs.set_het_rows(True)
+    if het_markers:
+        bs.set_het_markers(True)
 
     distributed = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if distributed else 0
@@ -644,6 +656,10 @@ def parse_args(argv=None):
     ap.add_argument("--het-rows", action="store_true",
                     help="with --het or --het-batch-vars: level 1 of both stages on the row-streaming kernel at per-pair sample "
                          "sizes instead of the exact sweep (`mps cusk ... het rows`); same files")
+    ap.add_argument("--het-markers", action="store_true",
+                    help="with --het or --het-batch-vars: every pair of markers is tested at the number of individuals both were "
+                         "genotyped on (.bed code 01 = missing) instead of all of them (`mps cusk ... het markers`); the files "
+                         "change where markers have missing calls")
     ap.add_argument("--no-stage", action="store_true", help="do not keep the whole .bed in HBM; every block uploads its slice")
     ap.add_argument("--device", type=int, default=None, help="GPU of this rank (default LOCAL_RANK modulo the device count)")
     args = ap.parse_args(argv)
@@ -659,6 +675,8 @@ def parse_args(argv=None):
         ap.error("--het-filter applies to runs at per-pair sample sizes: give --het or --het-batch-vars with it")
     if args.het_rows and not args.het:
         ap.error("--het-rows applies to runs at per-pair sample sizes: give --het or --het-batch-vars with it")
+    if args.het_markers and not args.het:
+        ap.error("--het-markers applies to runs at per-pair sample sizes: give --het or --het-batch-vars with it")
     if args.batch_vars is None:
         args.batch_vars = 0 if args.het else 16384
     return args
@@ -698,7 +716,7 @@ def main(argv=None):
     writer = args.writer if (batch_vars > 0 or args.writer != "merge") else "rank0"  # (merge is part of the batched path)
     allr, stats, owned = run_job(bs, args.outdir, device, args.inflight, args.schedule, cdev, stage=not args.no_stage,
                                  options={"timing": 0}, writer=writer, batch_vars=batch_vars, blockfile=args.blocks, het=het_batch,
-                                 het_filter=args.het_filter, het_rows=args.het_rows)
+                                 het_filter=args.het_filter, het_rows=args.het_rows, het_markers=args.het_markers)
     dt = time.perf_counter() - t0
     if batch_vars > 0:
         tests = sum(int(s.tests[0]) + int(s.tests[1]) for s in stats)

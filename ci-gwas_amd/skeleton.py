@@ -437,6 +437,44 @@ class Engine:
         self._check(lib().cusk_pair_counts(self.h, bed_p, phen_p, _ptr(ix), k, m_total, int(N), int(p), _ptr(mxp_n), _ptr(pxp_n)))
         return mxp_n, pxp_n
 
+    def marker_pair_sizes(self, bed, N: int, N_dev: int, ld: int, k: int | None = None, marker_ix=None,
+                          m_total: int | None = None) -> None:
+        """cusk_marker_pair_sizes: float32 counts of the individuals on which both markers of a pair are not missing, over
+        the k x k corner of the device matrix at N_dev (leading dimension ld; call it after `ess_square`).  bed: host array
+        or DeviceArray; the markers are rows `marker_ix` (ascending) of its m_total rows, or its first k rows (default: all
+        rows of a host array)"""
+        clb = (int(N) + 3) // 4
+        if isinstance(bed, DeviceArray):
+            bed_p, rows = bed.ptr, bed.nbytes // clb
+        else:
+            bed = np.ascontiguousarray(bed, np.uint8)
+            bed_p, rows = _ptr(bed), bed.size // clb
+        m_total = int(rows if m_total is None else m_total)
+        ix = np.ascontiguousarray(marker_ix, np.int32) if marker_ix is not None else None
+        k = int(len(ix) if ix is not None else (m_total if k is None else k))
+        self._check(lib().cusk_marker_pair_sizes(self.h, bed_p, _ptr(ix), k, m_total, int(N), N_dev, int(ld)))
+
+    def marker_pair_sizes_batch(self, bed, N: int, m, base, n: int, N_dev: int, marker_ix=None, m_total: int | None = None) -> None:
+        """cusk_marker_pair_sizes_batch: `marker_pair_sizes` for the blocks of a batch in one launch.  Block b = m[b] markers
+        at the variables base[b] .. of the n x n allocation at N_dev (call it after `ess_square_batch`); marker_ix = the
+        .bed rows of all blocks in one list, block after block (a row may repeat; None = rows 0 .. sum(m) - 1)"""
+        clb = (int(N) + 3) // 4
+        if isinstance(bed, DeviceArray):
+            bed_p, rows = bed.ptr, bed.nbytes // clb
+        else:
+            bed = np.ascontiguousarray(bed, np.uint8)
+            bed_p, rows = _ptr(bed), bed.size // clb
+        m = np.ascontiguousarray(m, np.int32)
+        base = np.ascontiguousarray(base, np.int32)
+        if m.shape != base.shape or m.ndim != 1:
+            raise ValueError("marker_pair_sizes_batch: one marker count and one base per block")
+        ix = np.ascontiguousarray(marker_ix, np.int32) if marker_ix is not None else None
+        if ix is not None and ix.size != int(m.sum()):
+            raise ValueError("marker_pair_sizes_batch: marker_ix must hold sum(m) rows")
+        m_total = int(rows if m_total is None else m_total)
+        self._check(lib().cusk_marker_pair_sizes_batch(self.h, bed_p, _ptr(ix), m_total, int(N), len(m), _ptr(m), _ptr(base), int(n),
+                                                       N_dev))
+
     def pack_lower_tri(self, C_dev: int, n: int, k: int) -> np.ndarray:
         """the leading k x k block of the n x n device matrix as the `mxm` file holds it: lower triangle with diagonal,
         row-major, NaN -> 0 (cusk_pack_lower_tri)"""

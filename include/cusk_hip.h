@@ -364,6 +364,25 @@ int cusk_ess_square(cusk_engine *e, const float *mxp_ess, const float *pxp_ess, 
  * when the matrix is written. */
 int cusk_ess_square_batch(cusk_engine *e, const float *mxp_ess, const float *pxp_ess, int nblk, const int *m, const int *base,
                           size_t p, float n_uniform, int n, float *N_dev);
+/* The marker x marker part of a sample-size matrix from the genotypes: for the rows marker_ix[0 .. k-1] of a .bed of m_total
+ * rows (HOST array; ascending, distinct; NULL = rows 0 .. k-1; bed host or device-resident, as cusk_pair_counts takes them)
+ * N_dev[i * ld + j] = (float)count(i, j) for all i, j < k, where count(i, j) is the number of individuals 0 .. N-1 for which
+ * neither marker has the missing code 01 -- the individuals the Pearson correlation of the pair was formed on.  The diagonal
+ * receives the marker's own count (nothing reads it).  Cells outside the k x k corner are not touched, so the call goes
+ * AFTER cusk_ess_square on the same allocation (ld = m + p), which wrote n_uniform there.  Counts are exact integers and
+ * N < 2^24 (an argument error otherwise), so the floats are exact; no standard-error chain is applied (the reference has no
+ * file route for marker x marker sizes, and the sweep truncates a size to int).  The corner is bitwise symmetric by
+ * construction: a tile and its mirror image are stored from the same integers.  Bits of a row beyond individual N and the
+ * memory behind a row do not matter.  Returns when the corner is written. */
+int cusk_marker_pair_sizes(cusk_engine *e, const unsigned char *bed, const int *marker_ix, size_t k, size_t m_total, size_t N,
+                           float *N_dev, size_t ld);
+/* cusk_marker_pair_sizes for the blocks of a batch, in one launch: block b holds its m[b] markers at the variables base[b] ..
+ * base[b] + m[b] of the n x n allocation N_dev (leading dimension n; bases as cusk_ess_square_batch takes them) and receives
+ * its m[b] x m[b] counts there; nothing outside these corners is written, so the call goes after cusk_ess_square_batch.
+ * marker_ix: the .bed rows of all blocks in ONE list, block after block (sum of m[b] entries, each below m_total; a row may
+ * occur more than once, since a batch may name a block twice; NULL = rows 0 .. sum - 1). */
+int cusk_marker_pair_sizes_batch(cusk_engine *e, const unsigned char *bed, const int *marker_ix, size_t m_total, size_t N, int nblk,
+                                 const int *m, const int *base, int n, float *N_dev);
 /* Host only.  The sample size the mxp / pxp loaders of `cuskss` make of a correlation and its standard error:
  * ((1 - r^2) / se)^2 with their float / double mix (marker_trait_summary_stats.cpp:161-164). */
 float cusk_ess_from_se(float r, float se);
@@ -507,6 +526,12 @@ int cusk_blockset_set_het_filter(cusk_blockset *bs, int on);
  * rows`): level 1 on the row-streaming kernel at per-pair sample sizes.  Same files; 0 (default) leaves the engine's option
  * as it is.  Set it before running blocks. */
 int cusk_blockset_set_het_rows(cusk_blockset *bs, int on);
+/* on = 1: the same runs give every pair of markers of a block the number of individuals both were observed on
+ * (cusk_marker_pair_sizes / _batch after cusk_ess_square / _batch) instead of the number of individuals (`mps cusk ... het
+ * markers`).  The files CHANGE where markers have missing calls; the stage-two sizes follow through the gather.  An error
+ * (with a message in cusk_blockset_last_error) unless cusk_blockset_set_het(bs, 1) came first; on = 0 is always accepted.
+ * Set it before running blocks. */
+int cusk_blockset_set_het_markers(cusk_blockset *bs, int on);
 /* Forgets what the block set keeps for engine e -- its device scratch (block matrices) and the state of a correlation
  * build started ahead -- and releases that memory.  Call before destroying an engine that ran blocks of this set when the
  * set outlives it (cusk_blockset_close releases everything anyway). */

@@ -7,7 +7,7 @@
 The data set is the one `bench.py --full` generates for its whole-chromosome leg (bench.write_chromosome: unequal LD
 blocks of 500 SNPs on average, 20 traits), with gaps put into two traits: trait 1 is observed on 25 % of the individuals,
 trait 3 on 60 %.  It is run through the block driver (run_blocks.run_job, one GPU, writer "local": every block's five
-files are written) seven ways:
+files are written) nine ways:
   1. het, one block per engine run          (`run_blocks.py --het`)
   2. het, batched                           (`run_blocks.py --het-batch-vars V`)
   3. not het, batched                       (`run_blocks.py --batch-vars V`: what the het batch lacks -- the filter, the
@@ -16,9 +16,12 @@ files are written) seven ways:
   5. het with the filter, batched           (`run_blocks.py --het-batch-vars V --het-filter`)
   6. ... with filter and rows, per block    (`run_blocks.py --het --het-filter --het-rows`: level 1 on the row kernel)
   7. ... with filter and rows, batched      (`run_blocks.py --het-batch-vars V --het-filter --het-rows`)
-(ways 4-5 and 6-7 have a block set, and with it engines, of their own: the options stay set on an engine)
+  8. ... filter, rows and markers, per block (`run_blocks.py --het --het-filter --het-rows --het-markers`: pairs of markers at
+                                              the number of individuals both were genotyped on; the results differ from 6-7)
+  9. ... filter, rows and markers, batched   (`run_blocks.py --het-batch-vars V --het-filter --het-rows --het-markers`)
+(ways 4-5, 6-7 and 8-9 have a block set, and with it engines, of their own: the options stay set on an engine)
 One repeat = `--passes` passes of the job over the chromosome, timed on the host around work that ends with the files on
-disk; the seven ways alternate inside every repeat.  After one untimed warm-up repeat the tool prints, per way, the median
+disk; the nine ways alternate inside every repeat.  After one untimed warm-up repeat the tool prints, per way, the median
 of `--repeats` repeats in blocks/s, the spread (max - min) of the repeats, and the mean wall-clock phases of a pass as the
 pipeline reports them (ms; counts and sizes are part of corr; l1_tests / l1_exact: level-1 tests per pass and those the
 row kernel's filter sent to the exact form, ways 6-7 only).  CUSK_BATCH_PROF=1 in the environment adds the batch
@@ -79,6 +82,11 @@ def main():
         bs_hetfr.set_het(True)
         bs_hetfr.set_het_filter(True)
         bs_hetfr.set_het_rows(True)
+        bs_hetfrm = rb.BlockSet(gaps, stem, blocks, args.alpha, args.max_level, args.max_level_two, 1)
+        bs_hetfrm.set_het(True)
+        bs_hetfrm.set_het_filter(True)
+        bs_hetfrm.set_het_rows(True)
+        bs_hetfrm.set_het_markers(True)
         V = args.het_batch_vars
         ways = {
             "het_per_block": dict(bs=bs_het, batch_vars=0, het=False),
@@ -88,6 +96,8 @@ def main():
             "het_filter_batch": dict(bs=bs_hetf, batch_vars=V, het=True),
             "het_filter_rows_per_block": dict(bs=bs_hetfr, batch_vars=0, het=False),
             "het_filter_rows_batch": dict(bs=bs_hetfr, batch_vars=V, het=True),
+            "het_filter_rows_markers_per_block": dict(bs=bs_hetfrm, batch_vars=0, het=False),
+            "het_filter_rows_markers_batch": dict(bs=bs_hetfrm, batch_vars=V, het=True),
         }
         counter = [0]
 
@@ -129,7 +139,7 @@ def main():
             out["ways"][name] = {"blocks_per_s_median": round(statistics.median(r), 1), "spread": round(max(r) - min(r), 1),
                                  "repeats": [round(v, 1) for v in r], "blocks_written": written[name],
                                  "phase_ms_per_pass": {k: round(v, 3) for k, v in phases[name].items()}}
-            print(f"{name:26s} {statistics.median(r):9.1f} blocks/s (median of {len(r)}, spread {max(r) - min(r):.1f}), "
+            print(f"{name:34s} {statistics.median(r):9.1f} blocks/s (median of {len(r)}, spread {max(r) - min(r):.1f}), "
                   f"{written[name]} of {nb} blocks written, phases/pass {out['ways'][name]['phase_ms_per_pass']}", flush=True)
         a, b = out["ways"]["het_batch"], out["ways"]["het_per_block"]
         out["het_batch_over_per_block"] = round(a["blocks_per_s_median"] / b["blocks_per_s_median"], 2)
@@ -137,7 +147,9 @@ def main():
         # the filter against the same way without it: ratio of the medians, and whether the gain exceeds both spreads
         # ... and the row kernel at level 1 against the filtered way without it
         for plain, filt in (("het_per_block", "het_filter_per_block"), ("het_batch", "het_filter_batch"),
-                            ("het_filter_per_block", "het_filter_rows_per_block"), ("het_filter_batch", "het_filter_rows_batch")):
+                            ("het_filter_per_block", "het_filter_rows_per_block"), ("het_filter_batch", "het_filter_rows_batch"),
+                            ("het_filter_rows_per_block", "het_filter_rows_markers_per_block"),
+                            ("het_filter_rows_batch", "het_filter_rows_markers_batch")):
             f, g = out["ways"][filt], out["ways"][plain]
             out[filt + "_over_" + plain] = round(f["blocks_per_s_median"] / g["blocks_per_s_median"], 2)
             out[filt + "_faster_by_more_than_the_spread"] = bool(
@@ -146,6 +158,7 @@ def main():
         bs_plain.close()
         bs_hetf.close()
         bs_hetfr.close()
+        bs_hetfrm.close()
         print(json.dumps(out))
     finally:
         shutil.rmtree(indir, ignore_errors=True)
