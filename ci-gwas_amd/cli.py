@@ -17,8 +17,10 @@ mirror of cusk_postprocessing/sepselect.py (ci-gwas_amd/sepselect.py) and write 
 decide at the per-pair sample sizes a heterogeneous `cuskss-merged` run left in `cuskss_merged_ssz.mtx`.
 `merge-block-outputs` (ci-gwas.py:255-271, :459-464) and the post-step of a merged `cuskss` run (:452-456) use this
 package's mirror of the reference's merge module (ci-gwas_amd/merge.py), pinned by files the reference's own code
-wrote (tests/golden/merge).  The rest of the downstream (srfci, mvivw) is the reference's own code and consumes the
-files written here unchanged.
+wrote (tests/golden/merge).  `iv-candidates` and `check-ivs` write the instrument tables of the reference's
+cusk_postprocessing/check_mr_assumptions.py (`get_iv_candidates`, `check_ivs`; its CLI reaches them through `mvivw`) from a
+merged skeleton, the tests of `check-ivs` on the device (ci-gwas_amd/ivcheck.py).  The rest of the downstream (the R
+estimators of srfci and mvivw) is the reference's own code and consumes the files written here unchanged.
 """
 from __future__ import annotations
 
@@ -178,6 +180,31 @@ def _add_sepselect(sub):
         p.set_defaults(func=func)
 
 
+def _add_ivcheck(sub):
+    """the two tables of cusk_postprocessing/check_mr_assumptions.py"""
+    p = sub.add_parser("iv-candidates", help="List the instrument candidates of every (exposure, outcome) pair of a merged "
+                                             "skeleton")
+    p.add_argument("cusk_output_stem", metavar="cusk-output-stem", type=str, help="outdir + stem of merged cusk results")
+    p.set_defaults(func=run_iv_candidates)
+    p = sub.add_parser("check-ivs", help="Filter instruments and exposures under the MR assumptions (requires GPU)")
+    p.add_argument("cusk_output_stem", metavar="cusk-output-stem", type=str, help="outdir + stem of merged cusk results")
+    p.add_argument("num_samples", metavar="num-samples", type=TypeCheck(int, "num-samples", 1, None),
+                   help="number of samples used for computing correlations")
+    p.add_argument("--accept-alpha", type=TypeCheck(float, "accept-alpha", 0.0, 1.0), required=True,
+                   help="significance level at which a marginal dependence is accepted")
+    p.add_argument("--reject-alpha", type=TypeCheck(float, "reject-alpha", 0.0, 1.0), required=True,
+                   help="significance level of the conditional independence tests")
+    p.add_argument("--relaxed-local-faithfulness", action="store_true",
+                   help="do not ask for a marginal dependence of instrument and outcome")
+    p.add_argument("--check-reverse-causality", action="store_true",
+                   help="drop exposures that the outcome's own instruments point to as its effects")
+    p.add_argument("--het", action="store_true",
+                   help="decide at the per-pair sample sizes of <cusk-output-stem>_ssz.mtx (written by cuskss-merged --het) "
+                        "instead of num-samples, which is then not used")
+    p.add_argument("--out", type=str, default=None, help="output file (default <cusk-output-stem>_ivs.csv)")
+    p.set_defaults(func=run_check_ivs)
+
+
 def build_parser() -> argparse.ArgumentParser:
     parser = _Parser(prog="ci-gwas", description="cusk / cuskss steps of CI-GWAS on AMD Instinct MI355X")
     sub = parser.add_subparsers(required=True, title="subcommands")
@@ -190,6 +217,7 @@ def build_parser() -> argparse.ArgumentParser:
     _add_sumstats(sub)
     _add_merge(sub)
     _add_sepselect(sub)
+    _add_ivcheck(sub)
     return parser
 
 
@@ -328,6 +356,25 @@ def run_v_struct(args):
                                              het=args.het)
     merged_cusk.to_file(f"{os.path.dirname(args.cusk_result_stem)}/max_sep_min_pc")
     print("Sepselect / v-structs done.")
+
+
+def run_iv_candidates(args):
+    from .ivcheck import iv_candidates, write_csv
+
+    write_csv(f"{args.cusk_output_stem}_iv_candidates.csv", iv_candidates(args.cusk_output_stem))
+
+
+def run_check_ivs(args):
+    from .ivcheck import check_ivs, load, write_csv
+
+    data = load(args.cusk_output_stem, het=args.het)  # unreadable inputs are reported before an engine exists; read once
+    from .skeleton import Engine
+
+    rows = check_ivs(args.cusk_output_stem, args.num_samples, args.accept_alpha, args.reject_alpha,
+                     relaxed_local_faithfulness=args.relaxed_local_faithfulness,
+                     check_reverse_causality=args.check_reverse_causality, het=args.het, engine=Engine(0), data=data)
+    write_csv(args.out or f"{args.cusk_output_stem}_ivs.csv", rows)
+    print(f"check-ivs: {len(rows)} instrument rows.")
 
 
 def main(argv=None):

@@ -550,6 +550,54 @@ class Engine:
                                                     float(q), _ptr(sel), _ptr(sel_len), _ptr(flags), _ptr(ms)))
         return sel, sel_len[:npairs], flags[:npairs], float(ms[0])
 
+    def _iv_args(self, trait_corr, set_off, sets, item_x, item_y, item_set):
+        trait_corr = np.ascontiguousarray(trait_corr, np.float64)
+        set_off = np.ascontiguousarray(set_off, np.int32).reshape(-1)
+        if set_off.shape[0] == 0:
+            set_off = np.zeros(1, np.int32)
+        sets = np.ascontiguousarray(sets, np.int32).reshape(-1)
+        item_x = np.ascontiguousarray(item_x, np.int32).reshape(-1)
+        item_y = np.ascontiguousarray(item_y, np.int32).reshape(-1)
+        item_set = np.ascontiguousarray(item_set, np.int32).reshape(-1)
+        nitems = item_x.shape[0]
+        assert trait_corr.ndim == 2 and item_y.shape[0] == nitems and item_set.shape[0] == nitems
+        assert sets.shape[0] >= int(set_off[-1])
+        return trait_corr, set_off, sets, item_x, item_y, item_set, nitems
+
+    def iv_check(self, trait_corr, set_off, sets, item_x, item_y, item_set, thr, z=None, flags=None):
+        """Batched tests (x, y | S) of the instrument filter (cusk_iv_check): `sets[set_off[s]:set_off[s + 1]]` are the
+        trait ids of set s, `item_set` = -1 is the empty set, `thr[l]` the threshold at |S| = l (l = 0 .. p-1).  Returns
+        (z float64, flags int32, kernel_ms) in the caller's item order; `z` / `flags` may be given to be filled in place."""
+        trait_corr, set_off, sets, item_x, item_y, item_set, nitems = self._iv_args(trait_corr, set_off, sets, item_x, item_y,
+                                                                                    item_set)
+        n, p = trait_corr.shape
+        thr = np.ascontiguousarray(thr, np.float64)
+        assert thr.shape[0] >= p
+        z = np.zeros(max(nitems, 1), np.float64) if z is None else z
+        flags = np.zeros(max(nitems, 1), np.int32) if flags is None else flags
+        assert z.dtype == np.float64 and flags.dtype == np.int32 and z.shape[0] >= nitems and flags.shape[0] >= nitems
+        ms = np.zeros(1, np.float32)
+        self._check(lib().cusk_iv_check(self.h, _ptr(trait_corr), n, p, set_off.shape[0] - 1, _ptr(set_off), _ptr(sets), nitems,
+                                        _ptr(item_x), _ptr(item_y), _ptr(item_set), _ptr(thr), _ptr(z), _ptr(flags), _ptr(ms)))
+        return z[:nitems], flags[:nitems], float(ms[0])
+
+    def iv_check_het(self, trait_corr, set_off, sets, item_x, item_y, item_set, trait_n, q, z=None, flags=None):
+        """`iv_check` at per-pair sample sizes (cusk_iv_check_het): `trait_n` is the n x p int32 table of sample sizes in the
+        layout of `trait_corr`, `q` = norm.ppf(1 - alpha / 2)."""
+        trait_corr, set_off, sets, item_x, item_y, item_set, nitems = self._iv_args(trait_corr, set_off, sets, item_x, item_y,
+                                                                                    item_set)
+        n, p = trait_corr.shape
+        trait_n = np.ascontiguousarray(trait_n, np.int32)
+        assert trait_n.shape == (n, p)
+        z = np.zeros(max(nitems, 1), np.float64) if z is None else z
+        flags = np.zeros(max(nitems, 1), np.int32) if flags is None else flags
+        assert z.dtype == np.float64 and flags.dtype == np.int32 and z.shape[0] >= nitems and flags.shape[0] >= nitems
+        ms = np.zeros(1, np.float32)
+        self._check(lib().cusk_iv_check_het(self.h, _ptr(trait_corr), n, p, set_off.shape[0] - 1, _ptr(set_off), _ptr(sets),
+                                            nitems, _ptr(item_x), _ptr(item_y), _ptr(item_set), _ptr(trait_n), float(q),
+                                            _ptr(z), _ptr(flags), _ptr(ms)))
+        return z[:nitems], flags[:nitems], float(ms[0])
+
     def corr_timing(self):
         t = np.zeros(4, np.float32)
         lib().cusk_corr_timing(self.h, _ptr(t))

@@ -456,6 +456,37 @@ int cusk_sepselect_greedy_het(cusk_engine *e, const double *trait_corr, long lon
                               const int *cand, const int *trait_n, const int *pair_n, double q, int *sel, int *sel_len,
                               int *flags, float *kernel_ms);
 
+/* `check-ivs` hot loop: the conditional-independence tests of cusk_postprocessing/check_mr_assumptions.py:14-26 (_indep)
+ * for a batch of items (x, y | S), with the conditioning sets given once and shared by the items that name them.  All
+ * pointers are HOST memory.
+ *   trait_corr  n x p doubles, row-major, as for cusk_sepselect_greedy (n >= p, symmetric on the trait rows)
+ *   set_off     nsets + 1 offsets into set, set_off[0] = 0; set = trait ids.  At most 127 per set, no duplicate
+ *   item_x/y    the tested pair (variable indices, distinct, at least one of them a trait: trait_corr holds no
+ *               marker x marker entry); neither may lie in the item's own set
+ *   item_set    the item's set, or -1 for the empty set (z of the raw correlation)
+ *   thr         thr[l] = norm.ppf(1 - alpha/2) / sqrt(num_samples - l - 3), l = 0 .. p-1: one call serves one alpha
+ * Out, in the caller's item order: z[k] = |0.5 log|(1 + rho)/(1 - rho)|| with rho the partial correlation of x and y given
+ * S, from the 2 x 2 Schur complement of S (W = C[S,S]^-1 by Gauss-Jordan with partial pivoting, once per set):
+ * rho = (c_xy - c_xS' W c_yS) / sqrt(|(1 - c_xS' W c_xS)(1 - c_yS' W c_yS)|) -- the reference's value from the inverse
+ * over [x, y] + S up to rounding.  flags[k] bit 0 = independent (z < thr[|S|]; a NaN on either side compares false:
+ * dependent, nothing is special-cased); flags[k] >> 8 = 0 ok, 2 = the set's sub-matrix is exactly singular (z is NaN
+ * then; items of other sets are not affected).
+ * Argument errors (CUSK_ERR_ARG, message in cusk_last_error, nothing launched): a set longer than 127, a duplicate or
+ * an id outside [0, p) in a set, an item whose x or y lies in its set or outside [0, n), x equal to y, x and y both
+ * markers, a set index outside [-1, nsets).
+ * kernel_ms (may be NULL): device time of the set-up and item kernels alone. */
+int cusk_iv_check(cusk_engine *e, const double *trait_corr, long long n, int p, int nsets, const int *set_off, const int *set,
+                  long long nitems, const int *item_x, const int *item_y, const int *item_set, const double *thr, double *z,
+                  int *flags, float *kernel_ms);
+/* The same tests, each decided at the sample sizes of the variables it is about: thr is replaced by trait_n (n x p int32,
+ * layout of trait_corr, symmetric on the trait x trait block) and q = norm.ppf(1 - alpha/2).  A test over V = {x, y} + S,
+ * |S| = l, is decided against q / sqrt(mean - l - 3), mean = (64-bit sum of the sizes of all (l + 2)(l + 1) / 2 unordered
+ * pairs of V) / that count: the rule of cusk_sepselect_greedy_het.  z does not depend on the sizes; with every size equal
+ * to N the mean is exactly N and flags equal those of cusk_iv_check with the table built from N. */
+int cusk_iv_check_het(cusk_engine *e, const double *trait_corr, long long n, int p, int nsets, const int *set_off,
+                      const int *set, long long nitems, const int *item_x, const int *item_y, const int *item_set,
+                      const int *trait_n, double q, double *z, int *flags, float *kernel_ms);
+
 /* out_host[a*k + b] = M_dev[idx[a]*n + idx[b]]: the retained sub-matrix of parent_set.cpp:84-238
  * (reduce_gc / reduce_gcs) without copying the n*n matrix to the host; idx_host has k entries. */
 int cusk_gather_submatrix(cusk_engine *e, const float *M_dev, int n, const int *idx_host, int k, float *out_host);
