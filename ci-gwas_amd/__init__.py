@@ -16,6 +16,7 @@ from .skeleton import (  # noqa: F401
     cu_corr_pearson_npn,
     cu_marker_phen_corr_pearson,
     ess_from_se,
+    hanning_weights,
     hetcor_skeleton,
     hetcor_threshold,
     se_from_count,

@@ -132,6 +132,8 @@ SYMBOLS = {
     "cusk_corr_timing": (None, [_vp, _vp]),
     "cusk_corr_banded": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "cusk_hanning_smooth": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "cusk_hanning_weights": (_i, [_i, _vp]),
+    "cusk_block_chr": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _sz, _vp]),
     "cusk_sepselect_greedy": (_i, [_vp, _vp, C.c_longlong, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "cusk_sepselect_greedy_het": (_i, [_vp, _vp, C.c_longlong, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
     "cusk_iv_check": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

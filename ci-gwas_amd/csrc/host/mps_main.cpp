@@ -22,7 +22,6 @@
 
 #include "../../../include/cusk_hip.h"
 #include "block_pipeline.h"
-#include "blocking.h"
 #include "host_io.h"
 
 using namespace host;
@@ -737,18 +736,15 @@ int cmd_block(int argc, char **argv)
         tm.mark("banded correlations + row sums (device)");
         std::cout << "[Chr " << cid << "]: Computing row sums." << std::endl;
         std::cout << "[Chr " << cid << "]: Making blocks." << std::endl;
-        const std::vector<ChrBlock> blocks =
-            blocks_of_chromosome(row_sums, max_block_size, [&](const std::vector<float> &v, const std::vector<double> &w) {
-                std::vector<double> out(v.size());
-                if (cusk_hanning_smooth(e, v.data(), v.size(), w.data(), (int)w.size(), out.data()) != CUSK_OK)
-                    engine_die("Hanning smoothing", e);
-                return out;
-            });
+        std::vector<long long> first(m), last(m);  // a chromosome has at most m blocks
+        size_t num_blocks = 0;
+        if (cusk_block_chr(e, row_sums.data(), m, max_block_size, first.data(), last.data(), m, &num_blocks) != CUSK_OK)
+            engine_die("Hanning smoothing", e);
         tm.mark("smoothing (device) + minima + bisection");
-        std::cout << "[Chr " << cid << "]: Partitioned into " << blocks.size() << " blocks." << std::endl;
+        std::cout << "[Chr " << cid << "]: Partitioned into " << num_blocks << " blocks." << std::endl;
         std::cout << "[Chr " << cid << "]: Writing blocks to output file." << std::endl;
         std::ofstream fout(out_path, std::ios::out | std::ios::app);  // io.cpp:266-277: appends
-        for (const ChrBlock &b : blocks) fout << cid << "\t" << b.first << "\t" << b.last << std::endl;
+        for (size_t b = 0; b < num_blocks; b++) fout << cid << "\t" << first[b] << "\t" << last[b] << std::endl;
     }
     cusk_engine_destroy(e);
     std::cout << "Done." << std::endl;

@@ -114,6 +114,14 @@ def se_from_count(r: float, count: int) -> float:
     return float(lib().cusk_se_from_count(float(np.float32(r)), int(count)))
 
 
+def hanning_weights(window: int) -> np.ndarray:
+    """cusk_hanning_weights (host only): the window weights `mps block` smooths with, single-precision cosine"""
+    out = np.zeros(max(int(window), 1), np.float64)
+    if lib().cusk_hanning_weights(int(window), _ptr(out)) != 0:
+        raise ValueError(f"cusk_hanning_weights: bad window {window}")
+    return out[: int(window)]
+
+
 def sumstats_write_se(outdir: str, mxp, mxp_n, pxp, pxp_n, chr_ids, snp_ids, ref_alleles, trait_names) -> None:
     """cusk_sumstats_write_se (host only): <outdir>/mxp_se.txt, pxp_se.txt from the correlations sumstats_write wrote and
     the per-pair observation counts of Engine.pair_counts (mxp_n m_total x p, pxp_n p x p)"""
@@ -501,6 +509,29 @@ class Engine:
         band = np.zeros((m, width), np.float32) if want_band else None
         self._check(lib().cusk_corr_banded(self.h, _ptr(bed), m, N, width, _ptr(sums), _ptr(band)))
         return (sums, band) if want_band else sums
+
+    def hanning_smooth(self, v, weights, out=None):
+        """cusk_hanning_smooth: out[c] = sum_i weights[i] * v[c - window // 2 + i] where the window fits, 0 elsewhere
+        (float64, accumulated in window order on the device).  `out` may be given (float64, at least len(v) entries) to
+        be filled in place; the first len(v) entries are returned."""
+        v = np.ascontiguousarray(v, np.float32)
+        weights = np.ascontiguousarray(weights, np.float64)
+        n = v.shape[0]
+        out = np.zeros(max(n, 1), np.float64) if out is None else out
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape[0] >= n
+        self._check(lib().cusk_hanning_smooth(self.h, _ptr(v), n, _ptr(weights), weights.shape[0], _ptr(out)))
+        return out[:n]
+
+    def block_chr(self, row_sums, max_block_size: int) -> list[tuple[int, int]]:
+        """cusk_block_chr, the code of `mps block` for one chromosome: (first, last) chromosome-local marker indices of
+        the LD blocks cut from the forward row sums"""
+        v = np.ascontiguousarray(row_sums, np.float32)
+        n = v.shape[0]
+        first = np.zeros(max(n, 1), np.int64)
+        last = np.zeros(max(n, 1), np.int64)
+        count = C.c_size_t(0)
+        self._check(lib().cusk_block_chr(self.h, _ptr(v), n, int(max_block_size), _ptr(first), _ptr(last), n, C.byref(count)))
+        return [(int(first[k]), int(last[k])) for k in range(count.value)]
 
     def sepselect_greedy(self, trait_corr, pair_i, pair_j, pair_corr, cand_off, cand, thr):
         """Batched greedy separating-set selection (sepselect.py:262-329) on the device.  Returns

@@ -416,6 +416,19 @@ int cusk_corr_banded(cusk_engine *e, const unsigned char *bed, size_t m, size_t 
  * the window weights (0.5 - 0.5 cosf(2 pi i / (window - 1)), blocking.cpp:8-11).  All pointers are host memory. */
 int cusk_hanning_smooth(cusk_engine *e, const float *v_host, size_t n, const double *weight_host, int window,
                         double *out_host);
+/* Host only.  The window weights `mps block` hands to cusk_hanning_smooth: out[i] = 0.5 - 0.5 cosf(2 pi i / (window - 1)),
+ * single-precision cosine (blocking.cpp:8-11), i = 0 .. window-1.  window = 1 gives NaN (0 / 0), as in the reference.
+ * CUSK_ERR_ARG for window <= 0 or a null pointer. */
+int cusk_hanning_weights(int window, double *out);
+/* block_chr, blocking.cpp:102-136: forward row sums of ONE chromosome (cusk_corr_banded) to its LD blocks -- the odd
+ * smoothing window is bisected between 3 and n until the largest block is within 100 of, and not above, max_block_size
+ * or the window stops moving; each step smooths on the device (cusk_hanning_smooth with cusk_hanning_weights) and cuts at
+ * the strict local minima on the host.  This is the code `mps block` runs.  first / last (host, cap entries each)
+ * receive the chromosome-local marker indices of the blocks, inclusive, in order; *count their number.  n blocks are
+ * always enough.  CUSK_ERR_ARG with *count = the number needed when cap is smaller (nothing is written then), and for
+ * n = 0 or a null pointer; an error of the smoothing is passed on (message in cusk_last_error). */
+int cusk_block_chr(cusk_engine *e, const float *row_sums, size_t n, int max_block_size, long long *first, long long *last,
+                   size_t cap, size_t *count);
 
 /* `sepselect` / `orient-v-structs` hot loop: cusk_postprocessing/sepselect.py:262-329
  * (MergedCuskResults.find_maximal_and_min_pcorr_sepsets_incr) for a batch of outer pairs, one wavefront per pair.

@@ -5,6 +5,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from test_blocking_cases import BANDED_EDGE_CASES, SMALL_CHROMOSOMES, SMALL_MAXB, SMALL_N, SMALL_WIDTH, is_cover
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MPS = os.path.join(ROOT, "ci-gwas_amd", "csrc", "mps")
@@ -152,10 +154,13 @@ def test_error_paths(tmp_path):
     assert r.returncode != 0
 
 
-@pytest.mark.parametrize("m,N,width", [(700, 600, 150), (333, 1001, 64), (130, 256, 129)])
+@pytest.mark.parametrize("m,N,width", [(700, 600, 150), (333, 1001, 64), (130, 256, 129)] + BANDED_EDGE_CASES)
 def test_banded_correlations_match_oracle(oracle, synth, m, N, width):
     """cusk_corr_banded (the FP4 contingency kernel restricted to a band) against the oracle: band and forward row
-    sums bit-exact; widths that do and do not divide the tile, N with and without partial K blocks"""
+    sums bit-exact; widths that do and do not divide the tile, N with and without partial K blocks; and the shapes
+    at which the number of band tiles per row tile and the clamps at the last marker change (BANDED_EDGE_CASES: width 1,
+    one marker, less than / exactly / just over one and two tiles, widths around 64 and 128, bands wider than the
+    chromosome), where the entries past the last marker are exactly 0"""
     import cigwas_amd as cg
 
     bed, _phen, _means, _stds, _G = synth.synth_bed_block(m, N, 1, block_index=23, miss=0.01)
@@ -165,6 +170,9 @@ def test_banded_correlations_match_oracle(oracle, synth, m, N, width):
     want = oracle.marker_corr_banded(bed, m, N, width)
     assert np.array_equal(band, want, equal_nan=True)
     assert np.array_equal(sums, oracle.banded_row_abs_sums(want))
+    if width >= m - 1:
+        past = np.arange(m)[:, None] + 1 + np.arange(width)[None, :] >= m
+        assert past.any() and np.array_equal(band[past].view(np.int32), np.zeros(int(past.sum()), np.int32))
 
 
 def test_mps_block_file_matches_oracle_pipeline(oracle, synth, tmp_path):
@@ -189,6 +197,25 @@ def test_mps_block_file_matches_oracle_pipeline(oracle, synth, tmp_path):
     assert open(path).read().splitlines() == want + want
     # the block file drives `mps cusk` unchanged
     assert oracle.read_blocks(path)[: len(want)] is not None
+
+
+def test_mps_block_file_at_small_chromosomes(oracle, synth, tmp_path):
+    """`mps block` on chromosomes of 3, 64, 65 and 400 markers whose ids are not in sorted order, band width 2, and an N
+    that is no multiple of 64 (rows that are not 16-byte multiples: the banded kernel without the prefetch): the .blocks
+    file equals the oracle's, chromosome after chromosome in .bim order (inputs checked in test_blocking_cases.py)"""
+    sizes = [m for _, m in SMALL_CHROMOSOMES]
+    bed, _phen, means, stds, _G = synth.synth_bed_block(sum(sizes), SMALL_N, 1, block_index=37)
+    chr_ids = [c for c, m in SMALL_CHROMOSOMES for _ in range(m)]
+    stem = str(tmp_path / "g")
+    synth.write_bfiles(stem, bed, SMALL_N, means, stds, chr_ids)
+    txt = _run(["block", stem, str(SMALL_MAXB), "1", str(SMALL_WIDTH)])
+    for c, m in SMALL_CHROMOSOMES:
+        assert f"[Chr {c}]: Loading bed data for {m} markers." in txt
+    want = oracle.make_blocks(bed, chr_ids, SMALL_N, SMALL_MAXB, SMALL_WIDTH)
+    got = open(f"{stem}_m{SMALL_MAXB}.blocks").read().splitlines()
+    assert got == want and len(want) > len(sizes)
+    for c, m in SMALL_CHROMOSOMES:
+        assert is_cover([tuple(map(int, l.split("\t")[1:])) for l in got if l.split("\t")[0] == c], m)
 
 
 def test_mps_block_refuses_band_wider_than_the_chromosome(synth, tmp_path):
