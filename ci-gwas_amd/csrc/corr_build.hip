@@ -1547,15 +1547,8 @@ int corr_build_batch_impl(cusk_engine *e, int phase, const unsigned char *bed_de
     const size_t o_t = (b_blk + 15) & ~(size_t)15, o_k = o_t + ((b_t + 15) & ~(size_t)15), total = o_k + ((b_k + 15) & ~(size_t)15) + 16;
     // one pinned staging area per phase: phase one waits for its stream at the end, phase two is followed by a run that does
     const int slot = phase == 1 ? 0 : 1;
-    if (total > e->corr_tab_pinned_cap[slot])
-    {
-        if (e->corr_tab_pinned[slot]) (void)hipHostFree(e->corr_tab_pinned[slot]);
-        e->corr_tab_pinned[slot] = nullptr;
-        e->corr_tab_pinned_cap[slot] = 0;
-        CUSK_HIP(e, hipHostMalloc(&e->corr_tab_pinned[slot], total * 2));
-        e->corr_tab_pinned_cap[slot] = total * 2;
-    }
-    char *h = static_cast<char *>(e->corr_tab_pinned[slot]);
+    CUSK_HIP(e, e->corr_tab_pinned[slot].ensure(total, total * 2));
+    char *h = e->corr_tab_pinned[slot].as<char>();
     std::memcpy(h, blk.data(), b_blk);
     if (phase == 1)
         std::memcpy(h + o_t, tiles2.data(), b_t);
@@ -1616,16 +1609,9 @@ int corr_build_batch_impl(cusk_engine *e, int phase, const unsigned char *bed_de
         if (async_mxp)
         {  // cusk_corr_build_batch: the correlations land in pinned memory, an event marks their arrival, nobody waits here
             const size_t cnt = (size_t)moff * p;
-            if (cnt > e->mxp_pinned_cap)
-            {
-                if (e->mxp_pending) return fail(e, CUSK_ERR_STATE, "a correlation build is in flight");
-                if (e->mxp_pinned) (void)hipHostFree(e->mxp_pinned);
-                e->mxp_pinned = nullptr;
-                e->mxp_pinned_cap = 0;
-                CUSK_HIP(e, hipHostMalloc(reinterpret_cast<void **>(&e->mxp_pinned), sizeof(float) * (cnt + cnt / 4 + 64)));
-                e->mxp_pinned_cap = cnt + cnt / 4 + 64;
-            }
-            if (mxp_d) CUSK_HIP(e, hipMemcpyAsync(e->mxp_pinned, mxp_d, sizeof(float) * cnt, hipMemcpyDeviceToHost, s));
+            if (sizeof(float) * cnt > e->mxp_pinned.cap && e->mxp_pending) return fail(e, CUSK_ERR_STATE, "a correlation build is in flight");
+            CUSK_HIP(e, e->mxp_pinned.ensure(sizeof(float) * cnt, sizeof(float) * (cnt + cnt / 4 + 64)));
+            if (mxp_d) CUSK_HIP(e, hipMemcpyAsync(e->mxp_pinned.p, mxp_d, sizeof(float) * cnt, hipMemcpyDeviceToHost, s));
             if (!e->ev_mxp) CUSK_HIP(e, hipEventCreateWithFlags(&e->ev_mxp, hipEventDisableTiming));
             CUSK_HIP(e, hipEventRecord(e->ev_mxp, s));
             return CUSK_OK;
@@ -1797,7 +1783,7 @@ extern "C" int cusk_corr_build_batch(cusk_engine *e, const unsigned char *bed_de
     CUSK_HIP(e, hipEventSynchronize(e->ev_mxp));
     size_t cnt = 0;
     for (int b = 0; b < nblk; b++) cnt += (size_t)markers[b] * p;
-    std::memcpy(mxp_host, e->mxp_pinned, sizeof(float) * cnt);
+    std::memcpy(mxp_host, e->mxp_pinned.p, sizeof(float) * cnt);
     return CUSK_OK;
 }
 
@@ -1806,15 +1792,8 @@ extern "C" int cusk_corr_build_begin(cusk_engine *e, const unsigned char *bed_de
 {
     if (!e || !C_dev || p == 0) return e ? fail(e, CUSK_ERR_ARG, "bad arguments") : CUSK_ERR_ARG;
     if (e->mxp_pending) return fail(e, CUSK_ERR_ARG, "a correlation build is already in flight");
-    if (m * p > e->mxp_pinned_cap)
-    {
-        if (e->mxp_pinned) (void)hipHostFree(e->mxp_pinned);
-        e->mxp_pinned = nullptr;
-        e->mxp_pinned_cap = 0;
-        CUSK_HIP(e, hipHostMalloc(reinterpret_cast<void **>(&e->mxp_pinned), sizeof(float) * (m * p + m * p / 4 + 64)));
-        e->mxp_pinned_cap = m * p + m * p / 4 + 64;
-    }
-    const int rc = corr_build_impl(e, bed_dev, phen_dev, m, N, p, mean_dev, std_dev, C_dev, e->mxp_pinned, nullptr, nullptr, true);
+    CUSK_HIP(e, e->mxp_pinned.ensure(sizeof(float) * m * p, sizeof(float) * (m * p + m * p / 4 + 64)));
+    const int rc = corr_build_impl(e, bed_dev, phen_dev, m, N, p, mean_dev, std_dev, C_dev, e->mxp_pinned.as<float>(), nullptr, nullptr, true);
     if (rc == CUSK_OK) e->mxp_pending = m * p;
     return rc;
 }
@@ -1829,7 +1808,7 @@ extern "C" int cusk_corr_build_end(cusk_engine *e, float *mxp_host)
     const size_t count = e->mxp_pending;
     e->mxp_pending = 0;
     CUSK_HIP(e, hipStreamSynchronize(e->stream3));
-    if (mxp_host) std::memcpy(mxp_host, e->mxp_pinned, sizeof(float) * count);
+    if (mxp_host) std::memcpy(mxp_host, e->mxp_pinned.p, sizeof(float) * count);
     return CUSK_OK;
 }
 

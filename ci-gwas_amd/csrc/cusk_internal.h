@@ -58,6 +58,32 @@ struct DevBuf
     }
 };
 
+// grow-only pinned host staging; the caller names the size to allocate when `need` bytes no longer fit
+struct PinnedBuf
+{
+    void *p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t need, size_t alloc)
+    {
+        if (need <= cap) return hipSuccess;
+        release();
+        hipError_t e = hipHostMalloc(&p, alloc);
+        if (e == hipSuccess) cap = alloc;
+        return e;
+    }
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <typename T>
+    T *as() const
+    {
+        return reinterpret_cast<T *>(p);
+    }
+};
+
 struct LevelCounters;  // sweep_common.h
 struct HostGate;       // sweep_common.h
 
@@ -69,8 +95,8 @@ struct cusk_engine
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;  // auxiliary stream: independent degree classes, off-critical-path kernels
     hipStream_t stream3 = nullptr;  // correlation build of the NEXT block while this one is swept (cusk_corr_build_begin / _end)
-    float *mxp_pinned = nullptr;    // pinned landing buffer of the prefetched marker x trait correlations
-    size_t mxp_pinned_cap = 0, mxp_pending = 0;  // floats; mxp_pending > 0: a build is in flight on stream3
+    cusk::PinnedBuf mxp_pinned;  // pinned landing buffer of the prefetched marker x trait correlations
+    size_t mxp_pending = 0;      // floats; mxp_pending > 0: a build is in flight on stream3
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_z = nullptr;
     hipEvent_t ev_mxp = nullptr;  // cusk_corr_build_batch: the marker x trait correlations have landed in mxp_pinned
     bool own_stream = false;
@@ -103,10 +129,8 @@ struct cusk_engine
     // batched runs (cusk_run_skeleton_batch): block table of the last run and its per-row view on the device
     std::vector<int> batch_lo, batch_hi;
     cusk::DevBuf row_range, row_blk, blk_woff;
-    void *batch_pinned = nullptr;  // staging of the per-row tables
-    size_t batch_pinned_cap = 0;
-    void *res_pinned = nullptr;    // cusk_result_sepsets_view: x, y, S of the records
-    size_t res_pinned_cap = 0;
+    cusk::PinnedBuf batch_pinned;  // staging of the per-row tables
+    cusk::PinnedBuf res_pinned;    // cusk_result_sepsets_view: x, y, S of the records
     cusk::DevBuf rv, rpos, sel, wpre;  // level 1, row-streaming kernel: C[X, adj(X)] and {Y, reverse position, off, deg} per CSR slot
     cusk::DevBuf nv;                   // ... its HET form: ess_term(N[X, adj(X)]) beside rv
     int level1_form = -1;              // cusk_engine_level1_form: kernel of level 1 in the last run (-1: no level 1 ran)
@@ -120,7 +144,7 @@ struct cusk_engine
     std::vector<unsigned long long> binom_host;
     long long binom_rows = 0;  // rows of the device-resident binomial table
     // per level: what the level's plan kernel tells the host, written straight into pinned host memory (the host follows
-    // the device at a distance, engine.hip); run_seq tags the entries of the current run
+    // the device at a distance, level_loop.hip); run_seq tags the entries of the current run
     cusk::HostGate *hgate = nullptr, *hgate_dev = nullptr;
     int run_seq = 0;
     long long item_cap_cur = 0;         // capacity (entries) of the per-class work-item buffers
@@ -152,7 +176,7 @@ struct cusk_engine
     int opt_vec_threads = 64;     // workgroup size of sweep_vec_kernel for the first degree class (64 / 128 / 256)
     long long opt_item_cap = 1ll << 20;  // work items per degree class and level the buffers hold before they are grown
     int opt_lookahead = 2;               // levels the host may enqueue ahead of the counters it has seen
-    int opt_sync2 = 1;                   // the host reads level 2's gate record before it enqueues that level's sweeps (engine.hip)
+    int opt_sync2 = 1;                   // the host reads level 2's gate record before it enqueues that level's sweeps (level_loop.hip)
     int opt_l1_threads = 0;              // test hook: 256 / 512 forces that workgroup size of level1_rows2_kernel (0: level1_rows_threads chooses)
     int opt_l1_lds_row = 1;              // test hook: 0 forces the form of level1_rows2_kernel that gathers the row of C through L1/L2
     int opt_timing = 1;                  // per-level HIP events for cusk_stats' kernel_ms / level_ms (0: total only)
@@ -165,16 +189,14 @@ struct cusk_engine
     int shard_host_staging = 0;
     cusk_exchange_fn shard_fn = nullptr;
     void *shard_user = nullptr;
-    void *shard_host = nullptr;  // pinned staging buffer
-    size_t shard_host_cap = 0;
+    cusk::PinnedBuf shard_host;  // pinned staging buffer
 
     // correlation build scratch
     cusk::DevBuf bed_dev, phen_dev, mean_dev, std_dev, planes, mxp_dev, pxp_dev, mxp_bq;
     cusk::DevBuf pc_masks, pc_counts;  // cusk_pair_counts: trait masks in the .bed bit layout, the counts before their download
     cusk::DevBuf mp_bits;              // cusk_marker_pair_sizes: one validity bit per marker and individual, rows padded to whole slabs
     cusk::DevBuf corr_tab[2];  // batched build: block / tile tables of phase one (marker x trait) and two (marker x marker)
-    void *corr_tab_pinned[2] = {nullptr, nullptr};
-    size_t corr_tab_pinned_cap[2] = {0, 0};
+    cusk::PinnedBuf corr_tab_pinned[2];
     hipEvent_t ev_corr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float corr_ms[4] = {0, 0, 0, 0};
 };
@@ -196,6 +218,25 @@ inline int fail(cusk_engine *e, int code, const std::string &msg)
                               std::string(#call) + ": " + hipGetErrorString(_st) + " (" +        \
                                   __FILE__ + ":" + std::to_string(__LINE__) + ")");              \
     } while (0)
+
+// level_loop.hip: one skeleton run (every entry point of engine.hip ends here)
+struct RunArgs
+{
+    int mode;  // 0 Skeleton, 1 hetcor
+    const float *C;
+    const float *Ness;      // hetcor, may be null (uniform); Skeleton: not null = per-pair thresholds (cusk_run_skeleton_het)
+    float ess_uniform;      // hetcor uniform ESS
+    const int *Ginit;       // hetcor, device n*n or null
+    const float *Th;        // mode 0: host thresholds ; mode 1 and mode 0 with Ness: Th[0] = alpha/2 quantile
+    const int *time_index;  // host, n entries or null
+    int n;
+    int maxlevel;
+    // batched run: per row the column range of its block (device, n entries) and the largest range; nullptr = one block
+    const int2 *row_range = nullptr;
+    int max_span = 0;
+    long long level0_pairs = 0;  // unordered pairs inside the blocks (the level-0 tests of a batched run)
+};
+int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st);
 
 // host-side helpers shared by the entry points
 void threshold_array_host(int n, float alpha, float *thr15);

@@ -45,6 +45,14 @@ struct LevelCounters
     unsigned long long next_item[kNumClasses];
 };
 
+// layout of the per-run control block (device) and of its pinned mirror (host)
+constexpr size_t kCtlCnt = 0;
+constexpr size_t kCtlSlots = (kCtlCnt + sizeof(LevelCounters) * kLevels + 15) & ~(size_t)15;
+constexpr size_t kCtlRecBase = (kCtlSlots + sizeof(unsigned long long) * kLevels * kCounterSlots * 4 + 15) & ~(size_t)15;
+constexpr size_t kCtlCanon = (kCtlRecBase + sizeof(long long) * (kLevels + 1) + 15) & ~(size_t)15;
+constexpr size_t kCtlSym = (kCtlCanon + sizeof(unsigned long long) * kLevels * kCounterSlots + 15) & ~(size_t)15;
+constexpr size_t kCtlBytes = kCtlSym + 16;
+
 // What the host needs to know about a level to follow the device, written by the level's plan kernel straight into
 // pinned host memory (no copy, no event on the stream); seq = the run's sequence number, stored last.
 struct HostGate

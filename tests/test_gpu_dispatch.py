@@ -1,6 +1,6 @@
 """The level sweep's kernel families against the oracle, by degree class.
 
-The engine picks a kernel per level and degree class (engine.hip, launch_level_sweeps): the level-1 row / pair /
+The engine picks a kernel per level and degree class (level_loop.hip, launch_sweeps): the level-1 row / pair /
 generic kernels, sweep_vec (64, 128 or 256 threads on class 0), sweep_fast (plain and HET), sweep_tmaj, sweep_exact and
 recheck, each staged in LDS or not.  The inputs (synth.dispatch_case, checked on the oracle by
 tests/test_dispatch_cases.py) put hub rows at every class boundary, removals at work-item boundaries, second passing

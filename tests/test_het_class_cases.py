@@ -140,7 +140,7 @@ def test_sizes_change_the_graph_in_the_rows_of_the_class(oracle, name, form):
 
 
 def test_het_stages_three_classes_and_reads_two_through_the_cache():
-    """what the engine derives (engine.hip: staged classes while lds_layout(cap, het).total <= kLdsLimit): with the
+    """what the engine derives (level_loop.hip: staged classes while lds_layout(cap, het).total <= kLdsLimit): with the
     second copy of the sub-matrix classes 0-2 are staged and 3-4 are not; without it class 3 is staged too"""
     caps, limit = class_caps()
     assert caps == [39, 63, 127, 191]
