@@ -1,7 +1,7 @@
 // corr_index.hip -- correlation build over a marker index list, and the summary-statistic layouts of its result.
 //
 // `cuskss` on the union of the markers that all LD blocks selected (merged_blocks.ixs) wants the LD of those markers,
-// which lie scattered over every chromosome of the .bed.  The build kernels of corr_build.hip read a CONTIGUOUS range
+// which lie scattered over every chromosome of the .bed.  The build kernels of corr_mxm.hip / corr_mxp.hip read a CONTIGUOUS range
 // of .bed rows, so the selected rows (and their means / standard deviations) are first packed into a contiguous HBM
 // scratch by a row-gather kernel and the build kernels then run on that, unchanged: k * ceil(N/4) bytes of extra
 // traffic beside a contraction of O(k^2 N).  The other two kernels of this file turn the square in-HBM matrix into what

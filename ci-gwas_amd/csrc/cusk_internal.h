@@ -58,6 +58,15 @@ struct DevBuf
     }
 };
 
+// a DevBuf that lives for one call: released when its scope ends, on error returns too
+struct ScopedDevBuf : DevBuf
+{
+    ScopedDevBuf() = default;
+    ScopedDevBuf(const ScopedDevBuf &) = delete;
+    ScopedDevBuf &operator=(const ScopedDevBuf &) = delete;
+    ~ScopedDevBuf() { release(); }
+};
+
 // grow-only pinned host staging; the caller names the size to allocate when `need` bytes no longer fit
 struct PinnedBuf
 {
@@ -242,7 +251,7 @@ int run_levels(cusk_engine *e, const RunArgs &a, cusk_stats *st);
 void threshold_array_host(int n, float alpha, float *thr15);
 float hetcor_threshold_host(float alpha);
 
-// corr_build.hip
+// corr_build.hip: the single build (its kernels: corr_mxm.hip, corr_mxp.hip behind corr_kernels.h)
 int corr_build_impl(cusk_engine *e, const unsigned char *bed, const float *phen, size_t m, size_t N,
                     size_t p, const float *mean, const float *std, float *C_dev, float *mxp_host,
                     float *mxm_tri_host, float *pxp_tri_host, bool ahead = false);

@@ -177,55 +177,147 @@ def test_corr_banded_against_ref64(cg, engines, synth, m, N, width):
         assert np.array_equal(b2, g_band, equal_nan=True) and np.array_equal(s2, g_sums, equal_nan=True)
 
 
-@pytest.mark.parametrize("N,p", [(1088, 22), (257, 43)])
-def test_corr_batch_against_ref64(cg, synth, N, p):
-    """the chromosome job's batched build (cusk_corr_build_batch, and _mxp + _mxm): blocks of 1, 63, 65 and 200 markers
-    whose first markers are not multiples of 64, on the diagonal of one allocation"""
-    from cigwas_amd._lib import lib
+SENTINEL = np.float32(-7.0)  # fills the batch allocation before a build: what the build leaves alone still holds it
 
-    L = lib()
-    M = 340
-    G, Y = ref64.make_case(M, N, p, seed=N + p, miss=0.01)
-    mean, sd = ref64.stats(G)
+
+class _BatchCase:
+    """the chromosome job's batched build: blocks of 1, 63, 65 and 200 markers whose first markers are not multiples of
+    64, on the diagonal of one allocation; the inputs live on the device once per (N, p)"""
+
     first = np.array([5, 6, 69, 134], np.int64)
     sizes = np.array([1, 63, 65, 200], np.int32)
-    base, b = [], 0
-    for k in sizes:
-        base.append(b)
-        b = (b + int(k) + p + 63) // 64 * 64
-    base, n = np.array(base, np.int32), b
-    dev = [cg.DeviceArray(np.ascontiguousarray(a)) for a in (synth.pack_bed(G), Y.reshape(-1), mean, sd)]
-    results = []
-    for split in (False, True):
-        e = cg.Engine(0)
-        Cd = cg.DeviceArray(nbytes=4 * n * n)
-        mxp_host = np.zeros(int(sizes.sum()) * p, np.float32)
-        args = [e.h] + [d.ptr for d in dev] + [N, p, len(sizes), first.ctypes.data, sizes.ctypes.data, base.ctypes.data]
-        if split:
-            assert L.cusk_corr_build_batch_mxp(*args, n, Cd.ptr, mxp_host.ctypes.data) == 0
-            assert L.cusk_corr_build_batch_mxm(*args, None, n, Cd.ptr) == 0
-        else:
-            assert L.cusk_corr_build_batch(*args, n, Cd.ptr, mxp_host.ctypes.data) == 0
-        sq = np.empty((n, n), np.float32)
-        assert L.cusk_engine_download(e.h, sq.ctypes.data, C.c_void_p(Cd.ptr), sq.nbytes) == 0
-        Cd.free()
-        e.close()
-        results.append((sq, mxp_host))
-    for d in dev:
-        d.free()
+
+    def __init__(self, cg, synth, N, p):
+        self.cg, self.N, self.p = cg, N, p
+        self.G, self.Y = ref64.make_case(340, N, p, seed=N + p, miss=0.01)
+        self.mean, self.sd = ref64.stats(self.G)
+        base, b = [], 0
+        for k in self.sizes:
+            base.append(b)
+            b = (b + int(k) + p + 63) // 64 * 64
+        self.base, self.n = np.array(base, np.int32), b
+        self.dev = [cg.DeviceArray(np.ascontiguousarray(a)) for a in (synth.pack_bed(self.G), self.Y.reshape(-1), self.mean, self.sd)]
+        self._default = self._refs = None
+
+    def free(self):
+        for d in self.dev:
+            d.free()
+
+    def build(self, e, split, keep=None):
+        """-> (the n x n allocation, mxp_host) after cusk_corr_build_batch (split: _mxp + _mxm, with the keep mask)"""
+        from cigwas_amd._lib import lib
+
+        L, n, p = lib(), self.n, self.p
+        Cd = self.cg.DeviceArray(np.full((n, n), SENTINEL, np.float32))
+        mxp_host = np.zeros(int(self.sizes.sum()) * p, np.float32)
+        args = [e.h] + [d.ptr for d in self.dev] + [self.N, p, len(self.sizes), self.first.ctypes.data, self.sizes.ctypes.data,
+                                                    self.base.ctypes.data]
+        try:
+            if split:
+                keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+                assert L.cusk_corr_build_batch_mxp(*args, n, Cd.ptr, mxp_host.ctypes.data) == 0
+                assert L.cusk_corr_build_batch_mxm(*args, None if keep_a is None else keep_a.ctypes.data, n, Cd.ptr) == 0
+            else:
+                assert keep is None
+                assert L.cusk_corr_build_batch(*args, n, Cd.ptr, mxp_host.ctypes.data) == 0
+            sq = np.empty((n, n), np.float32)
+            assert L.cusk_engine_download(e.h, sq.ctypes.data, C.c_void_p(Cd.ptr), sq.nbytes) == 0
+        finally:
+            Cd.free()
+        return sq, mxp_host
+
+    def build_with(self, opts):
+        """the one-call entry and the split entries, each on a fresh engine with the options set"""
+        out = []
+        for split in (False, True):
+            e = self.cg.Engine(0)
+            for k, v in opts.items():
+                e.set_option(k, v)
+            try:
+                out.append(self.build(e, split))
+            finally:
+                e.close()
+        return out
+
+    def default(self):
+        if self._default is None:
+            self._default = self.build_with({})
+        return self._default
+
+    def refs(self):
+        if self._refs is None:
+            self._refs = [_reference(self.G[f:f + k], self.Y, self.mean[f:f + k], self.sd[f:f + k], self.N, 1)[0]
+                          for f, k in zip(self.first, self.sizes)]
+        return self._refs
+
+    def blocks(self):
+        return [(int(f), int(k), int(b0)) for f, k, b0 in zip(self.first, self.sizes, self.base)]
+
+
+@pytest.fixture(scope="module")
+def batch_cases(cg, synth):
+    cache = {}
+
+    def get(N, p):
+        if (N, p) not in cache:
+            cache[(N, p)] = _BatchCase(cg, synth, N, p)
+        return cache[(N, p)]
+
+    yield get
+    for c in cache.values():
+        c.free()
+
+
+@pytest.mark.parametrize("path", list(PATHS))
+@pytest.mark.parametrize("N,p", [(1088, 22), (257, 43)])
+def test_corr_batch_against_ref64(batch_cases, N, p, path):
+    """cusk_corr_build_batch, and _mxp + _mxm, under every engine option of the single build.  The batch takes its SNP x
+    trait form from corr_mxp_f32 alone and always counts SNP x SNP on the FP4 pipe: corr_popcount and corr_fp4 = 0 must
+    leave every bit of the allocation and of mxp_host as the default engine leaves them."""
+    case = batch_cases(N, p)
+    opts, _ = PATHS[path]
+    form = "f32" if opts.get("corr_mxp_f32") else "bf16"
+    results = case.default() if not opts else case.build_with(opts)
+    if path in ("popcount", "fp4_0"):
+        for (sq, mxp_host), (sq0, mxp0) in zip(results, case.default()):
+            assert np.array_equal(sq, sq0, equal_nan=True) and np.array_equal(mxp_host, mxp0, equal_nan=True), path
     assert np.array_equal(results[0][1], results[1][1], equal_nan=True)
     sq, mxp_host = results[0]
     off = 0
-    for f, k, b0 in zip(first, sizes, base):
-        k = int(k)
-        Gb = G[f:f + k]
-        ref, _ = _reference(Gb, Y, mean[f:f + k], sd[f:f + k], N, 1)
+    written = np.zeros(sq.shape, bool)
+    for (f, k, b0), ref in zip(case.blocks(), case.refs()):
         blk = sq[b0:b0 + k + p, b0:b0 + k + p]
+        written[b0:b0 + k + p, b0:b0 + k + p] = True
         iu, ip = np.triu_indices(k, 1), np.triu_indices(p, 1)
         got = (blk[:k, :k][iu], blk[:k, k:], blk[k:, k:][ip])
-        _check(f"batch block {f}+{k}", got, ref, Y, sd[f:f + k], N, "bf16")
+        _check(f"batch block {f}+{k}", got, ref, case.Y, case.sd[f:f + k], N, form)
         assert np.array_equal(mxp_host[off:off + k * p].reshape(k, p), blk[:k, k:], equal_nan=True)
         assert np.array_equal(blk[k:, :k], blk[:k, k:].T, equal_nan=True)
+        assert np.array_equal(blk[:k, :k], blk[:k, :k].T, equal_nan=True) and np.array_equal(blk[k:, k:], blk[k:, k:].T, equal_nan=True)
         assert np.all(np.diag(blk) == 1)
         assert np.array_equal(results[1][0][b0:b0 + k + p, b0:b0 + k + p], blk, equal_nan=True)  # _mxp + _mxm
         off += k * p
+    assert np.all(sq[~written] == SENTINEL) and np.all(results[1][0][~written] == SENTINEL)  # nothing outside the blocks
+
+
+def test_corr_batch_keep_mask(cg, batch_cases):
+    """cusk_corr_build_batch_mxm builds the SNP x SNP part, the trait x trait part and the diagonal of the kept blocks
+    only; the SNP x trait strips of every block are phase one's (cusk_corr_build_batch_mxp), whatever is kept"""
+    N, p = 257, 43
+    case = batch_cases(N, p)
+    sq0, mxp0 = case.default()[1]  # _mxp + _mxm, every block kept
+    e = cg.Engine(0)
+    try:
+        for keep in ([1, 0, 1, 0], [0, 0, 0, 0]):
+            sq, mxp_host = case.build(e, True, keep)
+            want = np.full(sq.shape, SENTINEL, np.float32)
+            for (f, k, b0), kp in zip(case.blocks(), keep):
+                if kp:
+                    want[b0:b0 + k + p, b0:b0 + k + p] = sq0[b0:b0 + k + p, b0:b0 + k + p]
+                else:
+                    want[b0:b0 + k, b0 + k:b0 + k + p] = sq0[b0:b0 + k, b0 + k:b0 + k + p]
+                    want[b0 + k:b0 + k + p, b0:b0 + k] = sq0[b0 + k:b0 + k + p, b0:b0 + k]
+            assert np.array_equal(sq, want, equal_nan=True), keep
+            assert np.array_equal(mxp_host, mxp0, equal_nan=True), keep
+    finally:
+        e.close()

@@ -26,7 +26,7 @@ static int failures = 0;
 static int smooth_calls = 0;
 static std::vector<int> windows_seen;
 
-// hanning_smooth_kernel of corr_build.hip, one "thread" per centre
+// hanning_smooth_kernel of corr_banded.hip, one "thread" per centre
 static std::vector<double> smooth_stand_in(const std::vector<float> &v, const std::vector<double> &w)
 {
     const long long n = (long long)v.size();

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Build-time ISA check of the hand-issued .bed prefetch in mxm_fp4_kernel<true> (csrc/corr_build.hip).
+"""Build-time ISA check of the hand-issued .bed prefetch in mxm_fp4_kernel<true> (csrc/corr_mxm.hip).
 
 The kernel requests packed genotypes two K blocks ahead with inline-assembly `global_load_dwordx4` instructions and
 waits for them with counted `s_waitcnt vmcnt(2)` (the compiler's own waits would drain the queue).  The compiler does
