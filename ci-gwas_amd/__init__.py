@@ -19,6 +19,7 @@ from .skeleton import (  # noqa: F401
     hanning_weights,
     hetcor_skeleton,
     hetcor_threshold,
+    prune_write,
     se_from_count,
     sumstats_write,
     sumstats_write_se,

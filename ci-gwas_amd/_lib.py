@@ -134,6 +134,11 @@ SYMBOLS = {
     "cusk_hanning_smooth": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "cusk_hanning_weights": (_i, [_i, _vp]),
     "cusk_block_chr": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _sz, _vp]),
+    "cusk_genotype_counts": (_i, [_vp, _vp, _sz, _sz, _vp]),
+    "cusk_ld_prune_scan": (_i, [_vp, _vp, _vp, _sz, _sz, _vp]),
+    "cusk_ld_prune": (_i, [_vp, _vp, _sz, _sz, _sz, _f, _vp, _vp]),
+    "cusk_ld_prune_timing": (None, [_vp, _vp]),
+    "cusk_prune_write": (_i, [C.c_char_p, C.c_char_p, _vp, _sz]),
     "cusk_sepselect_greedy": (_i, [_vp, _vp, C.c_longlong, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "cusk_sepselect_greedy_het": (_i, [_vp, _vp, C.c_longlong, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
     "cusk_iv_check": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -7,7 +7,12 @@ positional / optional arguments, same range checks, same conversion to the posit
 the native `mps` program with literal 'NULL' for absent paths, `subprocess.run(check=True)`.
 `cuskss-het` and `cuskss-merged` (README.md:65,75 of the reference names them, its CLI does
 not define them) are aliases of `cuskss` that insist on the flags that select that mode.
-Two things the reference leaves to the user: `sumstats` writes the three correlation files of `cuskss` from a
+The workflow is prune-bed -> prep-bed -> block -> cusk -> merge-block-outputs -> cuskss-merged -> sepselect -> check-ivs.
+`prune-bed` is not in the reference: its README asks for a fileset that is LD pruned ("or at least does not have markers
+with a correlation of 1") and has no marker without recorded variation, and leaves both to the user.  Here they are
+decided on the device, on the banded Kendall-npn correlation that `block` and the skeleton use (`mps prune`): markers in
+.bim order per chromosome, the first kept marker wins.  That is not PLINK's rule (Pearson r^2, higher MAF kept).
+Two more things the reference leaves to the user: `sumstats` writes the three correlation files of `cuskss` from a
 PLINK set and a .phen, and `cuskss-merged --bfiles --phen` runs the merged step straight from those.  For phenotypes
 with missing values `sumstats --se` adds the two standard-error files (from the number of individuals each pair was
 observed on) and `cuskss-merged --bfiles --phen --het` tests every pair at that number.
@@ -87,6 +92,22 @@ def _add_prep(sub):
     p = sub.add_parser("prep-bed", help="Prepare PLINK bed file for cusk")
     p.add_argument("bfiles", type=str, help="filestem of .bed, .bim, .fam fileset")
     p.set_defaults(func=prep_bed)
+
+
+def _add_prune(sub):
+    """not in ci-gwas.py: the reference's README asks for an LD-pruned fileset without constant markers and leaves it to
+    the user"""
+    p = sub.add_parser("prune-bed", help="Drop markers without recorded variation and LD-prune a PLINK fileset on the "
+                                         "correlation the skeleton tests; goes in front of prep-bed (requires GPU)")
+    p.add_argument("bfiles", type=str, help="filestem of .bed, .bim, .fam fileset")
+    p.add_argument("out", type=str, help="filestem of the pruned fileset; also receives .prune.in and .prune.out")
+    p.add_argument("--r-max", type=TypeCheck(float, "r-max", 0.0, 1.0), required=True,
+                   help="drop a marker when |r| >= r-max with an earlier kept marker of its chromosome within the window "
+                        "(banded Kendall-npn correlation, the one `block` and the skeleton use); in (0, 1].  The first kept "
+                        "marker wins: not PLINK's rule, which keeps the marker with the higher MAF")
+    p.add_argument("--window", type=TypeCheck(int, "window", 1, 4096), default=2000,
+                   help="number of following markers each marker is compared with (default: the corr-width of block)")
+    p.set_defaults(func=prune_bed)
 
 
 def _add_block(sub):
@@ -208,6 +229,7 @@ def _add_ivcheck(sub):
 def build_parser() -> argparse.ArgumentParser:
     parser = _Parser(prog="ci-gwas", description="cusk / cuskss steps of CI-GWAS on AMD Instinct MI355X")
     sub = parser.add_subparsers(required=True, title="subcommands")
+    _add_prune(sub)
     _add_prep(sub)
     _add_block(sub)
     _add_cusk(sub)
@@ -224,6 +246,20 @@ def build_parser() -> argparse.ArgumentParser:
 def prep_bed(args):
     """ci-gwas.py:386-387"""
     subprocess.run([MPS_PATH, "prep", args.bfiles], check=True)
+
+
+def prune_argv(args) -> list[str]:
+    """`mps prune <bfiles> <out-stem> <r-max> <window>`"""
+    if args.r_max == 0:
+        sys.exit("prune-bed: --r-max 0 would drop every marker that has a neighbour: give a value in (0, 1].")
+    if args.out == args.bfiles or any(os.path.exists(args.out + sfx) and os.path.exists(args.bfiles + sfx)
+                                      and os.path.samefile(args.out + sfx, args.bfiles + sfx) for sfx in (".bed", ".bim", ".fam")):
+        sys.exit("prune-bed: the output stem must differ from bfiles.")
+    return [MPS_PATH, "prune", args.bfiles, args.out, repr(float(args.r_max)), str(args.window)]
+
+
+def prune_bed(args):
+    subprocess.run(prune_argv(args), check=True)
 
 
 def block_argv(args) -> list[str]:

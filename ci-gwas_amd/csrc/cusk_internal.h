@@ -208,6 +208,8 @@ struct cusk_engine
     cusk::PinnedBuf corr_tab_pinned[2];
     hipEvent_t ev_corr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float corr_ms[4] = {0, 0, 0, 0};
+    float prune_ms[5] = {0, 0, 0, 0, 0};  // cusk_ld_prune_timing: upload, band, counts, bitmap, scan of the last cusk_ld_prune
+    hipEvent_t ev_prune[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // its phase marks, created by the first cusk_ld_prune
 };
 
 namespace cusk {

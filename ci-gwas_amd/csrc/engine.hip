@@ -126,6 +126,8 @@ extern "C" void cusk_engine_destroy(cusk_engine *e)
             if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : {e->ev_fork, e->ev_join, e->ev_z, e->ev_mxp})
         if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->ev_prune)
+        if (ev) (void)hipEventDestroy(ev);
     if (e->stream2) (void)hipStreamDestroy(e->stream2);
     if (e->stream3) (void)hipStreamDestroy(e->stream3);
     e->mxp_pinned.release();

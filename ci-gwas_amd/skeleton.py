@@ -122,6 +122,15 @@ def hanning_weights(window: int) -> np.ndarray:
     return out[: int(window)]
 
 
+def prune_write(bfiles: str, out_stem: str, status) -> None:
+    """cusk_prune_write (host only): <out_stem>.bed/.bim/.fam without the markers whose status (one byte per line of
+    <bfiles>.bim, as `Engine.ld_prune` gives them per chromosome) is not 0, and <out_stem>.prune.in / .prune.out"""
+    status = np.ascontiguousarray(status, np.uint8)
+    rc = lib().cusk_prune_write(str(bfiles).encode(), str(out_stem).encode(), _ptr(status), status.size)
+    if rc != 0:
+        raise RuntimeError(f"cusk_prune_write failed ({rc}): see stderr")
+
+
 def sumstats_write_se(outdir: str, mxp, mxp_n, pxp, pxp_n, chr_ids, snp_ids, ref_alleles, trait_names) -> None:
     """cusk_sumstats_write_se (host only): <outdir>/mxp_se.txt, pxp_se.txt from the correlations sumstats_write wrote and
     the per-pair observation counts of Engine.pair_counts (mxp_n m_total x p, pxp_n p x p)"""
@@ -509,6 +518,48 @@ class Engine:
         band = np.zeros((m, width), np.float32) if want_band else None
         self._check(lib().cusk_corr_banded(self.h, _ptr(bed), m, N, width, _ptr(sums), _ptr(band)))
         return (sums, band) if want_band else sums
+
+    def genotype_counts(self, bed, m: int, N: int, out=None) -> np.ndarray:
+        """cusk_genotype_counts: (m, 4) int32, per marker the individuals < N with .bed code 00, 01, 10, 11 (dosage 2,
+        missing, dosage 1, dosage 0).  `out` may be given (int32, at least 4 m entries) to be filled in place."""
+        bed = np.ascontiguousarray(bed, np.uint8)
+        if bed.size < int(m) * ((int(N) + 3) // 4):
+            raise ValueError("genotype_counts: bed holds fewer than m rows of ceil(N / 4) bytes")
+        out = np.zeros(4 * max(int(m), 1), np.int32) if out is None else out
+        assert out.dtype == np.int32 and out.flags.c_contiguous and out.size >= 4 * m
+        self._check(lib().cusk_genotype_counts(self.h, _ptr(bed), int(m), int(N), _ptr(out)))
+        return out.reshape(-1)[:4 * m].reshape(m, 4)
+
+    def ld_prune_scan(self, conflict_bits, constant_flags, m: int, W: int, out=None) -> np.ndarray:
+        """cusk_ld_prune_scan: the greedy pass of `ld_prune` alone on a conflict bitmap (m rows of ceil(W / 64) uint64
+        words, bit b of word k of row i = pair (i, i + 1 + 64 k + b)) and one constant flag per marker -> m status bytes
+        (0 kept, 1 constant, 2 dropped for LD).  `out` may be given (uint8, at least m entries)."""
+        bits = np.ascontiguousarray(conflict_bits, np.uint64)
+        flags = np.ascontiguousarray(constant_flags, np.uint8)
+        if bits.size != int(m) * ((int(W) + 63) // 64) or flags.size != int(m):
+            raise ValueError("ld_prune_scan: m rows of ceil(W / 64) words and m flags")
+        out = np.zeros(max(int(m), 1), np.uint8) if out is None else out
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= m
+        self._check(lib().cusk_ld_prune_scan(self.h, _ptr(bits), _ptr(flags), int(m), int(W), _ptr(out)))
+        return out[:m]
+
+    def ld_prune(self, bed, m: int, N: int, W: int, r_max: float, want_counts: bool = False):
+        """cusk_ld_prune for one chromosome: m status bytes (0 kept, 1 constant, 2 dropped for LD: |r| >= r_max with an
+        earlier kept marker within W, r the banded correlation of `corr_banded`); with want_counts also the (m, 4)
+        genotype counts.  The first kept marker wins (not PLINK's rule)."""
+        bed = np.ascontiguousarray(bed, np.uint8)
+        if bed.size < int(m) * ((int(N) + 3) // 4):
+            raise ValueError("ld_prune: bed holds fewer than m rows of ceil(N / 4) bytes")
+        status = np.zeros(max(int(m), 1), np.uint8)
+        counts = np.zeros((max(int(m), 1), 4), np.int32) if want_counts else None
+        self._check(lib().cusk_ld_prune(self.h, _ptr(bed), int(m), int(N), int(W), float(r_max), _ptr(status), _ptr(counts)))
+        return (status[:m], counts[:m]) if want_counts else status[:m]
+
+    def ld_prune_timing(self) -> dict:
+        """device milliseconds of the phases of the last `ld_prune` (cusk_ld_prune_timing)"""
+        ms = np.zeros(5, np.float32)
+        lib().cusk_ld_prune_timing(self.h, _ptr(ms))
+        return dict(zip(("upload", "band", "counts", "bitmap", "scan"), (float(v) for v in ms)))
 
     def hanning_smooth(self, v, weights, out=None):
         """cusk_hanning_smooth: out[c] = sum_i weights[i] * v[c - window // 2 + i] where the window fits, 0 elsewhere

@@ -430,6 +430,54 @@ int cusk_hanning_weights(int window, double *out);
 int cusk_block_chr(cusk_engine *e, const float *row_sums, size_t n, int max_block_size, long long *first, long long *last,
                    size_t cap, size_t *count);
 
+/* `mps prune`: the two things the workflow asks of a fileset before `prep-bed` -- no marker without recorded variation
+ * and no pair of markers with a correlation of 1 -- decided on the correlation the skeleton tests (the banded Kendall-npn
+ * values of cusk_corr_banded), per chromosome, markers in .bim order, j local to the chromosome:
+ *   counts(j)      individuals < N with .bed code 00, 01, 10, 11 (dosage 2, missing, dosage 1, dosage 0); the padding
+ *                  codes of the last byte when N % 4 != 0 are not individuals
+ *   constant(j)    at most one of the three non-missing counts is non-zero (an all-missing marker is constant)
+ *   r(i, j)        for 0 < j - i <= W: band[i * W + (j - i - 1)] of cusk_corr_banded(.., width = W, ..), the same bits
+ *   conflict(i, j) fabsf(r(i, j)) >= r_max as floats; NaN gives no conflict
+ *   keep(j)        !constant(j) and no i in [max(0, j - W), j) with keep(i) and conflict(i, j)
+ *   status(j)      CUSK_PRUNE_CONSTANT if constant, else CUSK_PRUNE_LD if not kept, else CUSK_PRUNE_KEEP
+ * A dropped or constant marker never blocks another: the first kept marker wins.  (PLINK's --indep-pairwise prunes on the
+ * Pearson r^2 of the dosages and keeps the marker with the higher minor allele frequency; this is neither.)
+ * All pointers are host memory.  Argument errors (CUSK_ERR_ARG, message in cusk_last_error, nothing launched): a null
+ * pointer, m == 0, N == 0, W == 0, W > CUSK_PRUNE_MAX_WINDOW, r_max not in (0, 1]. */
+enum
+{
+    CUSK_PRUNE_KEEP = 0,
+    CUSK_PRUNE_CONSTANT = 1,
+    CUSK_PRUNE_LD = 2
+};
+#define CUSK_PRUNE_MAX_WINDOW 4096 /* largest W of cusk_ld_prune and cusk_ld_prune_scan */
+/* counts_out[j * 4 + c] (int32) = counts(j) for code c = 00, 01, 10, 11, for the m rows of ceil(N / 4) bytes at bed. */
+int cusk_genotype_counts(cusk_engine *e, const unsigned char *bed, size_t m, size_t N, int *counts_out);
+/* The greedy pass alone, on a caller's conflict bitmap: row i holds ceil(W / 64) little-endian 64-bit words, bit b of
+ * word k stands for the pair (i, i + 1 + 64 k + b); constant_flags: one byte per marker (non-zero = constant);
+ * status_out: m bytes.  Bits of columns >= W and of pairs with i + 1 + 64 k + b >= m are ignored, whatever they hold. */
+int cusk_ld_prune_scan(cusk_engine *e, const unsigned long long *conflict_bits, const unsigned char *constant_flags, size_t m,
+                       size_t W, unsigned char *status_out);
+/* One chromosome: upload, the banded build of cusk_corr_banded, counts, bitmap, scan, download of the m status bytes (and
+ * of the m x 4 counts when counts_out is not NULL).  The float band (m * W * 4 bytes) stays on the device. */
+int cusk_ld_prune(cusk_engine *e, const unsigned char *bed, size_t m, size_t N, size_t W, float r_max, unsigned char *status_out,
+                  int *counts_out);
+/* device time of the phases of the last cusk_ld_prune: [0] upload, [1] band, [2] counts, [3] bitmap, [4] scan (ms) */
+void cusk_ld_prune_timing(const cusk_engine *e, float *ms5);
+/* Host only.  The fileset <bfiles> without the markers whose status (m_total bytes, one per line of <bfiles>.bim, as
+ * cusk_ld_prune gives them chromosome after chromosome) is not CUSK_PRUNE_KEEP:
+ *   <out_stem>.bed        the magic bytes, then the kept rows byte for byte
+ *   <out_stem>.bim        the kept lines unchanged
+ *   <out_stem>.fam        a copy
+ *   <out_stem>.prune.in   the kept SNP ids (column 2 of the .bim), one per line, in order
+ *   <out_stem>.prune.out  "id<TAB>constant" or "id<TAB>ld" per dropped marker, in order
+ * CUSK_ERR_ARG for a null pointer, m_total == 0, out_stem equal to bfiles or an output path that names one of the input
+ * files (another spelling, a link), a fileset that cannot be read or whose .bim does not have m_total lines or whose .bed
+ * is shorter than they need; CUSK_ERR_STATE when a file cannot be written in full.  A call that fails leaves none of the
+ * five files it would have created (files of these names from an earlier call may have been replaced by then, the input
+ * never).  The reason goes to stderr. */
+int cusk_prune_write(const char *bfiles, const char *out_stem, const unsigned char *status, size_t m_total);
+
 /* `sepselect` / `orient-v-structs` hot loop: cusk_postprocessing/sepselect.py:262-329
  * (MergedCuskResults.find_maximal_and_min_pcorr_sepsets_incr) for a batch of outer pairs, one wavefront per pair.
  * All pointers are HOST memory.
