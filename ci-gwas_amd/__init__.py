@@ -19,9 +19,11 @@ from .skeleton import (  # noqa: F401
     hanning_weights,
     hetcor_skeleton,
     hetcor_threshold,
+    ordinal_levels,
     prune_write,
     se_from_count,
     sumstats_write,
     sumstats_write_se,
+    sumstats_write_se_values,
     threshold_array,
 )

@@ -129,6 +129,12 @@ SYMBOLS = {
     "cusk_ess_from_se": (_f, [_f, _f]),
     "cusk_se_from_count": (_f, [_f, _i]),
     "cusk_sumstats_write_se": (_i, [C.c_char_p, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, C.c_char_p, _sz]),
+    "cusk_sumstats_write_se_values": (_i, [C.c_char_p, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, C.c_char_p, _sz]),
+    "cusk_ordinal_tables": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "cusk_polychoric_fit": (_i, [_vp, _vp, _sz, _i, _i, _vp, _vp, _vp]),
+    "cusk_polyserial_fit": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cusk_matrix_set_cross": (_i, [_vp, _vp, _sz, _sz, _vp]),
+    "cusk_ordinal_timing": (None, [_vp, _vp]),
     "cusk_corr_timing": (None, [_vp, _vp]),
     "cusk_corr_banded": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "cusk_hanning_smooth": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),

@@ -15,7 +15,8 @@ decided on the device, on the banded Kendall-npn correlation that `block` and th
 Two more things the reference leaves to the user: `sumstats` writes the three correlation files of `cuskss` from a
 PLINK set and a .phen, and `cuskss-merged --bfiles --phen` runs the merged step straight from those.  For phenotypes
 with missing values `sumstats --se` adds the two standard-error files (from the number of individuals each pair was
-observed on) and `cuskss-merged --bfiles --phen --het` tests every pair at that number.
+observed on) and `cuskss-merged --bfiles --phen --het` tests every pair at that number.  `--ordinal NAMES` on either
+marks binary or graded traits: their pairs get polychoric / polyserial correlations and standard errors.
 
 `sepselect` and `orient-v-structs` (ci-gwas.py:303-358, handlers :467-476) run this package's device-backed
 mirror of cusk_postprocessing/sepselect.py (ci-gwas_amd/sepselect.py) and write the same files.  With `--het` they
@@ -154,6 +155,9 @@ def _add_cuskss(sub, name, help_):
         p.add_argument("--het-markers", action="store_true",
                        help="with --bfiles and --het: also every pair of markers at the number of individuals both were "
                             "genotyped on instead of the number of individuals (`mps cuskss-bed ... het markers`)")
+        p.add_argument("--ordinal", type=str, default=None, metavar="NAMES",
+                       help="with --bfiles and --het: names (or 1-based numbers) of the ordinal traits, as `sumstats "
+                            "--ordinal` takes them; the result of cuskss-het on the files it writes")
     p.set_defaults(func=cuskss, variant=name)
 
 
@@ -168,6 +172,10 @@ def _add_sumstats(sub):
     p.add_argument("--se", action="store_true",
                    help="also write mxp_se.txt and pxp_se.txt (for cuskss --mxp-se/--pxp-se): standard errors from the number "
                         "of individuals each pair was observed on, for a .phen with NA entries")
+    p.add_argument("--ordinal", type=str, default=None, metavar="NAMES",
+                   help="comma-separated names (or 1-based numbers) of the traits of the .phen that are ordinal (2 to 8 "
+                        "distinct values, e.g. case/control): pairs with one of them get polychoric (marker or ordinal "
+                        "partner) or polyserial (continuous partner) correlations and standard errors; implies --se")
     p.set_defaults(func=sumstats)
 
 
@@ -286,8 +294,64 @@ def cusk_argv(args) -> list[str]:
                         ["markers"] if getattr(args, "het_markers", False) else [])
 
 
+NA_TOKENS = ("NA", "NaN", "nan", "NAN")  # is_na_token of csrc/host/host_io.h
+
+
+def ordinal_arg(command: str, names: str, phen_path: str) -> str:
+    """`--ordinal NAMES` -> `ordinal=<1-based,...>` of the native program: names are looked up in the header of the .phen
+    (two id columns, then the traits), numbers are taken as they are; every named trait must have 2 to 8 distinct
+    non-NA values.  `mps` checks the levels again on the table it loads; here the file is streamed once and only the
+    named columns are looked at, so that a wrong name or a continuous trait is an argument error before the GPU is asked
+    for."""
+    try:
+        f = open(phen_path)
+    except OSError:
+        sys.exit(f"{command}: cannot read {phen_path}.")
+    with f:
+        traits = f.readline().split()[2:]
+        numbers = []
+        for tok in names.split(","):
+            tok = tok.strip()
+            if tok in traits:
+                num = traits.index(tok) + 1
+            elif tok.isdigit():
+                num = int(tok)
+                if not 1 <= num <= len(traits):
+                    sys.exit(f"{command}: --ordinal trait number {num} is out of range (1 .. {len(traits)}).")
+            else:
+                sys.exit(f"{command}: --ordinal names an unknown trait '{tok}' (the .phen has: {' '.join(traits)}).")
+            if num in numbers:
+                sys.exit(f"{command}: --ordinal names trait '{tok}' twice.")
+            numbers.append(num)
+        limit = 4096  # enough to tell a graded trait from a continuous one without keeping all of the latter
+        distinct = {num: set() for num in numbers}
+        for line in f:
+            w = line.split()
+            for num, seen in distinct.items():
+                if len(seen) > limit or num + 1 >= len(w) or w[num + 1] in NA_TOKENS:
+                    continue
+                try:
+                    x = float(w[num + 1])
+                except ValueError:
+                    sys.exit(f"{command}: cannot read the value '{w[num + 1]}' of trait {traits[num - 1]}.")
+                if x == x:
+                    seen.add(x)
+    for num in numbers:
+        count = len(distinct[num])
+        shown = f"more than {limit}" if count > limit else str(count)
+        if count > 8:
+            sys.exit(f"{command}: --ordinal trait {traits[num - 1]} has {shown} distinct values; at most 8 levels are "
+                     "supported.")
+        if count < 2:
+            sys.exit(f"{command}: --ordinal trait {traits[num - 1]} has {shown} distinct values; at least 2 levels are "
+                     "needed.")
+    return "ordinal=" + ",".join(str(v) for v in numbers)
+
+
 def sumstats_argv(args) -> list[str]:
-    return [MPS_PATH, "sumstats", args.phen, args.bfiles, args.marker_indices, args.outdir] + (["se"] if args.se else [])
+    ordinal = getattr(args, "ordinal", None)
+    tail = ["se", ordinal_arg("sumstats", ordinal, args.phen)] if ordinal is not None else (["se"] if args.se else [])
+    return [MPS_PATH, "sumstats", args.phen, args.bfiles, args.marker_indices, args.outdir] + tail
 
 
 def sumstats(args):
@@ -302,6 +366,8 @@ def cuskss_bed_argv(args) -> list[str]:
         sys.exit("cuskss-merged: --bfiles and --phen go together.")
     if getattr(args, "het_markers", False) and not args.het:
         sys.exit("cuskss-merged: --het-markers applies to runs at per-pair sample sizes: give --het with it.")
+    if getattr(args, "ordinal", None) is not None and not args.het:
+        sys.exit("cuskss-merged: --ordinal estimates come with their own standard errors: give --het with it.")
     if any(v != "NULL" for v in (args.mxm, args.mxp, args.pxp)):
         sys.exit("cuskss-merged: give either --bfiles/--phen or --mxm/--mxp/--pxp, not both.")
     if args.mxp_se != "NULL" or args.pxp_se != "NULL":
@@ -322,7 +388,8 @@ def cuskss_bed_argv(args) -> list[str]:
                      f"{args.bfiles}.dim.")
     return [MPS_PATH, "cuskss-bed", args.phen, args.bfiles, args.marker_indices, args.time_index, str(args.alpha),
             str(args.max_level_one), str(args.max_level_two), str(args.max_depth), args.outdir] + (["het"] if args.het else []) + (
-                ["markers"] if getattr(args, "het_markers", False) else [])
+                ["markers"] if getattr(args, "het_markers", False) else []) + (
+                    [ordinal_arg("cuskss-merged", args.ordinal, args.phen)] if getattr(args, "ordinal", None) is not None else [])
 
 
 def cuskss_argv(args) -> list[str]:
@@ -333,6 +400,8 @@ def cuskss_argv(args) -> list[str]:
         sys.exit("cuskss-merged: --het needs --bfiles and --phen (with correlation files, give --mxp-se/--pxp-se).")
     if getattr(args, "het_markers", False):
         sys.exit("cuskss-merged: --het-markers needs --bfiles, --phen and --het (correlation files carry no marker x marker sizes).")
+    if getattr(args, "ordinal", None) is not None:
+        sys.exit("cuskss-merged: --ordinal needs --bfiles, --phen and --het (correlation files already hold their estimates).")
     if args.pxp == "NULL":
         sys.exit("the following arguments are required: --pxp")
     if args.num_samples is None:

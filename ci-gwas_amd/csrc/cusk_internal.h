@@ -209,6 +209,7 @@ struct cusk_engine
     hipEvent_t ev_corr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float corr_ms[4] = {0, 0, 0, 0};
     float prune_ms[5] = {0, 0, 0, 0, 0};  // cusk_ld_prune_timing: upload, band, counts, bitmap, scan of the last cusk_ld_prune
+    float ord_ms[3] = {0, 0, 0};  // cusk_ordinal_timing: table kernel, polychoric fit kernel, polyserial fit kernel of their last calls
     hipEvent_t ev_prune[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // its phase marks, created by the first cusk_ld_prune
 };
 

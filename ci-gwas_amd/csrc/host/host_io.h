@@ -354,7 +354,9 @@ inline Mxp load_mxp(const std::string &path, const std::string &se_path, const s
                 {
                     const float r = std::stof(w[j]);
                     out.corr.push_back(r);
-                    if (het) out.ess.push_back(ess_from_se(r, std::stof(ws[j])));
+                    // a correlation on the boundary of its estimator has no standard error (NA in mxp_se): no sample size
+                    if (het)
+                        out.ess.push_back(is_na_token(ws[j], true) ? std::numeric_limits<float>::quiet_NaN() : ess_from_se(r, std::stof(ws[j])));
                 }
             }
             ++out.num_markers;

@@ -7,8 +7,8 @@
 //   mps cuskss <mxm> <mxp> <mxp_se> <pxp> <pxp_se> <time_index> <block_index> <blockfile>
 //              <marker_indices> <alpha> <l1> <l2> <depth> <num_samples> <outdir>   ("NULL" = absent)
 // and two commands the reference does not have, for users who hold the genotypes (see SUMSTATS_USAGE):
-//   mps sumstats   <.phen> <bfiles> <marker-indices|NULL> <outdir> [se]
-//   mps cuskss-bed <.phen> <bfiles> <marker-indices> <time_index|NULL> <alpha> <l1> <l2> <depth> <outdir> [het]
+//   mps sumstats   <.phen> <bfiles> <marker-indices|NULL> <outdir> [se] [ordinal=<1-based,...>]
+//   mps cuskss-bed <.phen> <bfiles> <marker-indices> <time_index|NULL> <alpha> <l1> <l2> <depth> <outdir> [het] [markers] [ordinal=<1-based,...>]
 //   mps prune      <bfiles> <out-stem> <r-max> <window>   (see PRUNE_USAGE)
 // Differences by design: the correlation matrix never leaves HBM between the build and the
 // sweep, adjacency comes back as a bitmap, separating sets as sparse records, only the
@@ -25,6 +25,7 @@
 #include "../../../include/cusk_hip.h"
 #include "block_pipeline.h"
 #include "host_io.h"
+#include "ordinal_host.h"
 
 using namespace host;
 
@@ -330,7 +331,7 @@ int cmd_cuskss(int argc, char **argv)
 const char *SUMSTATS_USAGE = R"(
 Compute the summary statistics cuskss reads (mxm, mxp, pxp) from genotypes and phenotypes.
 
-usage: mps sumstats <.phen> <bfiles> <marker-indices|NULL> <outdir> [se]
+usage: mps sumstats <.phen> <bfiles> <marker-indices|NULL> <outdir> [se] [ordinal=<1-based,...>]
 
 arguments:
     .phen           path to standardized phenotype tsv
@@ -339,17 +340,23 @@ arguments:
     outdir          receives mxm.bin, mxp.txt (all markers), pxp.txt
     se              also write mxp_se.txt and pxp_se.txt: standard errors from the number of individuals each pair was
                     observed on (.phen with NA), for cuskss --mxp-se / --pxp-se
+    ordinal=...     (after se) 1-based numbers of the traits that are ordinal (2 to 8 distinct values): every pair with one of
+                    them gets its polychoric (marker or ordinal partner) or polyserial (continuous partner) correlation
+                    and that estimator's standard error instead of the Pearson value and the count's
 )";
 
 const char *CUSKSS_BED_USAGE = R"(
 Run cuskss on the markers selected in all blocks, with the correlations computed from genotypes on the device.
 
-usage: mps cuskss-bed <.phen> <bfiles> <marker-indices> <time_index|NULL> <alpha> <max_level_one> <max_level_two> <depth> <outdir> [het] [markers]
+usage: mps cuskss-bed <.phen> <bfiles> <marker-indices> <time_index|NULL> <alpha> <max_level_one> <max_level_two> <depth> <outdir> [het] [markers] [ordinal=<1-based,...>]
 
     het             test every marker-trait and trait-trait pair at the number of individuals it was observed on (.phen
                     with NA) instead of all of them: the result of cuskss on the files of `mps sumstats ... se`
     markers         (after het) also every pair of markers at the number of individuals both were genotyped on (.bed code
                     01 = missing) instead of all of them; cuskss_merged.ess carries those counts in its marker x marker part
+    ordinal=...     (after het) 1-based numbers of the ordinal traits: polychoric / polyserial correlations and their
+                    standard errors for every pair with one of them; the result of cuskss on the files of
+                    `mps sumstats ... se ordinal=...`
 )";
 
 // .phen, the prep files and the marker selection; the arrays every kernel reads are copied to the device once
@@ -462,6 +469,87 @@ struct GenoInputs
     }
 };
 
+// Polychoric / polyserial estimates of every pair with an ordinal trait (`ordinal=`), as float32 the files hold: r and se
+// are formed in double on the device and rounded once, here.
+struct OrdinalTraitEstimates
+{
+    std::vector<float> r, se;  // p x q: trait a with ordinal trait spec.ix[t]; its own entry is not set
+};
+
+OrdinalSpec load_ordinal_spec(const std::string &arg, const GenoInputs &in)
+{
+    try
+    {
+        return ordinal_levels(parse_ordinal_arg(arg, in.p()), in.phen.data.data(), in.N(), in.trait_names);
+    }
+    catch (const std::exception &ex)
+    {
+        die(ex.what());
+    }
+    return OrdinalSpec();
+}
+
+OrdinalTraitEstimates ordinal_trait_estimates(cusk_engine *e, const GenoInputs &in, const OrdinalSpec &spec)
+{
+    const size_t p = in.p(), q = spec.q();
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    OrdinalTraitEstimates out;
+    out.r.assign(p * q, nan);
+    out.se.assign(p * q, nan);
+    std::vector<int> oxo(q * q * 64);
+    if (cusk_ordinal_tables(e, nullptr, in.phen_d, nullptr, 0, 0, in.N(), p, spec.ix.data(), q, spec.levels.data(), spec.nlev.data(),
+                            nullptr, oxo.data()) != CUSK_OK)
+        engine_die("ordinal trait tables", e);
+    std::vector<double> r(q * q), se(q * q);
+    std::vector<int> status(q * q);
+    if (cusk_polychoric_fit(e, oxo.data(), q * q, 8, 8, r.data(), se.data(), status.data()) != CUSK_OK)
+        engine_die("polychoric fit (traits)", e);
+    for (size_t a = 0; a < q; a++)
+        for (size_t b = a + 1; b < q; b++)
+        {  // one fit per pair, mirrored: the two orientations of a table need not agree to the last bit
+            out.r[(size_t)spec.ix[a] * q + b] = out.r[(size_t)spec.ix[b] * q + a] = (float)r[a * q + b];
+            out.se[(size_t)spec.ix[a] * q + b] = out.se[(size_t)spec.ix[b] * q + a] = (float)se[a * q + b];
+        }
+    std::vector<int> cont;
+    for (size_t t = 0; t < p; t++)
+        if (std::find(spec.ix.begin(), spec.ix.end(), (int)t) == spec.ix.end()) cont.push_back((int)t);
+    if (!cont.empty())
+    {
+        const size_t nc = cont.size();
+        r.resize(nc * q), se.resize(nc * q), status.resize(nc * q);
+        if (cusk_polyserial_fit(e, in.phen_d, in.N(), p, cont.data(), nc, spec.ix.data(), q, spec.levels.data(), spec.nlev.data(),
+                                r.data(), se.data(), status.data()) != CUSK_OK)
+            engine_die("polyserial fit", e);
+        for (size_t c = 0; c < nc; c++)
+            for (size_t t = 0; t < q; t++)
+            {
+                out.r[(size_t)cont[c] * q + t] = (float)r[c * q + t];
+                out.se[(size_t)cont[c] * q + t] = (float)se[c * q + t];
+            }
+    }
+    return out;
+}
+
+// r and se (rows x q, float32) of the markers `marker_ix` (NULL: rows 0 .. rows-1 of bed) with every ordinal trait
+void ordinal_marker_estimates(cusk_engine *e, const GenoInputs &in, const OrdinalSpec &spec, const unsigned char *bed, const int *marker_ix,
+                              size_t rows, size_t m_total, float *r_out, float *se_out)
+{
+    const size_t q = spec.q();
+    std::vector<int> tab(rows * q * 24);
+    if (cusk_ordinal_tables(e, bed, in.phen_d, marker_ix, rows, m_total, in.N(), in.p(), spec.ix.data(), q, spec.levels.data(),
+                            spec.nlev.data(), tab.data(), nullptr) != CUSK_OK)
+        engine_die("ordinal marker tables", e);
+    std::vector<double> r(rows * q), se(rows * q);
+    std::vector<int> status(rows * q);
+    if (cusk_polychoric_fit(e, tab.data(), rows * q, 3, 8, r.data(), se.data(), status.data()) != CUSK_OK)
+        engine_die("polychoric fit (markers)", e);
+    for (size_t i = 0; i < rows * q; i++)
+    {
+        r_out[i] = (float)r[i];
+        se_out[i] = (float)se[i];
+    }
+}
+
 int cmd_sumstats(int argc, char **argv)
 {
     if (argc < 6)
@@ -472,6 +560,9 @@ int cmd_sumstats(int argc, char **argv)
     const std::string phen_path = argv[2], bfiles = argv[3], index_path = argv[4], outdir = argv[5];
     const bool with_se = argc > 6;
     if (with_se && std::string(argv[6]) != "se") die(std::string("sumstats: unknown trailing argument ") + argv[6]);
+    const bool with_ordinal = argc > 7;
+    if (with_ordinal && std::string(argv[7]).compare(0, 8, "ordinal=") != 0) die(std::string("sumstats: unknown trailing argument ") + argv[7]);
+    if (argc > 8) die(std::string("sumstats: unknown trailing argument ") + argv[8]);
     PhaseTimer tm;
     check_path(outdir);
     GenoInputs in;
@@ -528,6 +619,44 @@ int cmd_sumstats(int argc, char **argv)
         tm.mark("genome-wide pair counts");
     }
 
+    // ordinal traits: their columns of mxp / mxp_se and their rows and columns of pxp / pxp_se are replaced
+    std::vector<float> pxp_out = pxp, mxp_se, pxp_se;
+    if (with_ordinal)
+    {
+        const OrdinalSpec spec = load_ordinal_spec(argv[7], in);
+        const size_t q = spec.q();
+        std::cout << "Estimating polychoric / polyserial correlations of " << q << " ordinal traits" << std::endl;
+        const float nan = std::numeric_limits<float>::quiet_NaN();
+        mxp_se.resize(m * p);
+        for (size_t i = 0; i < m * p; i++) mxp_se[i] = std::isnan(mxp[i]) ? nan : cusk_se_from_count(mxp[i], mxp_n[i]);
+        pxp_se.assign(p * p, nan);
+        for (size_t a = 0; a < p; a++)
+            for (size_t b = 0; b < p; b++)
+                if (a != b && !std::isnan(pxp[a * p + b])) pxp_se[a * p + b] = cusk_se_from_count(pxp[a * p + b], pxp_n[a * p + b]);
+        const OrdinalTraitEstimates te = ordinal_trait_estimates(e, in, spec);
+        for (size_t t = 0; t < q; t++)
+            for (size_t a = 0; a < p; a++)
+                if (a != (size_t)spec.ix[t])
+                {
+                    const size_t o = (size_t)spec.ix[t];
+                    pxp_out[a * p + o] = pxp_out[o * p + a] = te.r[a * q + t];
+                    pxp_se[a * p + o] = pxp_se[o * p + a] = te.se[a * q + t];
+                }
+        std::vector<float> r(chunk * q), se(chunk * q);
+        for (size_t c0 = 0; c0 < m; c0 += chunk)
+        {
+            const size_t mc = std::min(chunk, m - c0);
+            ordinal_marker_estimates(e, in, spec, in.bed_rows() + c0 * clb, nullptr, mc, mc, r.data(), se.data());
+            for (size_t i = 0; i < mc; i++)
+                for (size_t t = 0; t < q; t++)
+                {
+                    mxp[(c0 + i) * p + spec.ix[t]] = r[i * q + t];
+                    mxp_se[(c0 + i) * p + spec.ix[t]] = se[i * q + t];
+                }
+        }
+        tm.mark("ordinal tables + fits");
+    }
+
     std::cout << "Writing mxm.bin, mxp.txt, pxp.txt" << std::endl;
     auto cstrs = [](const std::vector<std::string> &v) {
         std::vector<const char *> out(v.size());
@@ -536,10 +665,17 @@ int cmd_sumstats(int argc, char **argv)
     };
     const auto chr = cstrs(in.chr), snp = cstrs(in.snp), ref = cstrs(in.ref), names = cstrs(in.trait_names);
     char err[512] = "";
-    if (cusk_sumstats_write(outdir.c_str(), tri.data(), k, mxp.data(), m, p, pxp.data(), chr.data(), snp.data(), ref.data(),
+    if (cusk_sumstats_write(outdir.c_str(), tri.data(), k, mxp.data(), m, p, pxp_out.data(), chr.data(), snp.data(), ref.data(),
                             names.data(), err, sizeof(err)) != CUSK_OK)
         die(err);
-    if (with_se)
+    if (with_ordinal)
+    {
+        std::cout << "Writing mxp_se.txt, pxp_se.txt" << std::endl;
+        if (cusk_sumstats_write_se_values(outdir.c_str(), mxp_se.data(), m, p, pxp_se.data(), chr.data(), snp.data(), ref.data(),
+                                          names.data(), err, sizeof(err)) != CUSK_OK)
+            die(err);
+    }
+    else if (with_se)
     {
         std::cout << "Writing mxp_se.txt, pxp_se.txt" << std::endl;
         if (cusk_sumstats_write_se(outdir.c_str(), mxp.data(), mxp_n.data(), m, p, pxp.data(), pxp_n.data(), chr.data(), snp.data(),
@@ -565,9 +701,18 @@ int cmd_cuskss_bed(int argc, char **argv)
     const std::string outdir = argv[10];
     const bool het = argc > 11;
     if (het && std::string(argv[11]) != "het") die(std::string("cuskss-bed: unknown trailing argument ") + argv[11]);
-    const bool het_markers = argc > 12;
-    if (het_markers && std::string(argv[12]) != "markers") die(std::string("cuskss-bed: unknown trailing argument ") + argv[12]);
-    if (argc > 13) die(std::string("cuskss-bed: unknown trailing argument ") + argv[13]);
+    bool het_markers = false;
+    std::string ordinal_arg;
+    for (int a = 12; a < argc; a++)
+    {  // after het: markers, then ordinal=...
+        const std::string w = argv[a];
+        if (w == "markers" && a == 12)
+            het_markers = true;
+        else if (w.compare(0, 8, "ordinal=") == 0 && a + 1 == argc)
+            ordinal_arg = w;
+        else
+            die(std::string("cuskss-bed: unknown trailing argument ") + argv[a]);
+    }
     if (index_path == "NULL") die("cuskss-bed needs marker indices");
     check_path(outdir);
     const bool time_indexed = time_index_path != "NULL";
@@ -634,6 +779,39 @@ int cmd_cuskss_bed(int argc, char **argv)
                 gc.ess[(k + a) * n + k + a] = nan;
                 for (size_t b = a + 1; b < p; b++)
                     gc.ess[(k + a) * n + k + b] = gc.ess[(k + b) * n + k + a] = ess_of(pxp[a * p + b], pxp_n[a * p + b]);
+            }
+        }
+        if (!ordinal_arg.empty())
+        {
+            // what `mps sumstats ... se ordinal=` writes for the pairs with an ordinal trait, through the same rounding to
+            // float32 and the same chain to a sample size; the matrix on the device gets the estimates in place
+            const OrdinalSpec spec = load_ordinal_spec(ordinal_arg, in);
+            const size_t q = spec.q();
+            std::cout << "Estimating polychoric / polyserial correlations of " << q << " ordinal traits" << std::endl;
+            const float nan = std::numeric_limits<float>::quiet_NaN();
+            auto ess_of_se = [&](float r, float se) { return std::isnan(r) ? nan : cusk_ess_from_se(r, se); };
+            const OrdinalTraitEstimates te = ordinal_trait_estimates(e, in, spec);
+            std::vector<float> mr(k * q), mse(k * q), cross(n);
+            ordinal_marker_estimates(e, in, spec, in.bed_rows(), in.ixs.data(), k, in.m(), mr.data(), mse.data());
+            for (size_t t = 0; t < q; t++)
+            {
+                const size_t o = k + (size_t)spec.ix[t];
+                for (size_t i = 0; i < k; i++)
+                {
+                    cross[i] = mr[i * q + t];
+                    gc.ess[i * n + o] = gc.ess[o * n + i] = ess_of_se(mr[i * q + t], mse[i * q + t]);
+                }
+                for (size_t a = 0; a < p; a++)
+                {
+                    if (k + a == o)
+                    {
+                        cross[o] = 1.0f;
+                        continue;
+                    }
+                    cross[k + a] = te.r[a * q + t];
+                    gc.ess[(k + a) * n + o] = gc.ess[o * n + k + a] = ess_of_se(te.r[a * q + t], te.se[a * q + t]);
+                }
+                if (cusk_matrix_set_cross(e, C.p, n, o, cross.data()) != CUSK_OK) engine_die("ordinal correlations into the matrix", e);
             }
         }
         // what the loaders of the three files do to a NaN correlation (host_io.h: load_mxm_into, load_mxp, load_pxp)

@@ -186,6 +186,29 @@ extern "C" int cusk_sumstats_write_se(const char *outdir, const float *mxp, cons
     return CUSK_OK;
 }
 
+// the two standard-error files from finished arrays (polychoric / polyserial standard errors do not come from a count)
+extern "C" int cusk_sumstats_write_se_values(const char *outdir, const float *mxp_se, size_t m_total, size_t p, const float *pxp_se,
+                                             const char *const *chr, const char *const *snp, const char *const *ref,
+                                             const char *const *trait_names, char *err, size_t err_len)
+{
+    auto report = [&](const std::string &msg, int code) {
+        if (err && err_len) std::snprintf(err, err_len, "%s", msg.c_str());
+        return code;
+    };
+    if (!outdir || !mxp_se || !pxp_se || !chr || !snp || !ref || !trait_names || m_total == 0 || p == 0)
+        return report("cusk_sumstats_write_se_values: bad arguments", CUSK_ERR_ARG);
+    try
+    {
+        write_mxp(host::make_path(outdir, "mxp_se", ".txt"), mxp_se, m_total, p, chr, snp, ref, trait_names);
+        write_pxp(host::make_path(outdir, "pxp_se", ".txt"), pxp_se, p, trait_names);
+    }
+    catch (const std::exception &ex)
+    {
+        return report(ex.what(), CUSK_ERR_ARG);
+    }
+    return CUSK_OK;
+}
+
 extern "C" int cusk_sumstats_write(const char *outdir, const float *mxm_tri, size_t k, const float *mxp, size_t m_total, size_t p,
                                    const float *pxp_square, const char *const *chr, const char *const *snp, const char *const *ref,
                                    const char *const *trait_names, char *err, size_t err_len)

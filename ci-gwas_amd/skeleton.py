@@ -155,6 +155,41 @@ def sumstats_write_se(outdir: str, mxp, mxp_n, pxp, pxp_n, chr_ids, snp_ids, ref
         raise RuntimeError(f"cusk_sumstats_write_se failed ({rc}): {err.value.decode()}")
 
 
+def sumstats_write_se_values(outdir: str, mxp_se, pxp_se, chr_ids, snp_ids, ref_alleles, trait_names) -> None:
+    """cusk_sumstats_write_se_values (host only): <outdir>/mxp_se.txt, pxp_se.txt from finished standard errors (mxp_se
+    m_total x p, pxp_se p x p with NaN on its diagonal), as `sumstats --ordinal` writes them"""
+    pxp_se = np.ascontiguousarray(pxp_se, np.float32)
+    p = pxp_se.shape[0]
+    mxp_se = np.ascontiguousarray(mxp_se, np.float32).reshape(-1, p)
+    m_total = mxp_se.shape[0]
+    if pxp_se.shape != (p, p):
+        raise ValueError("pxp_se must be p x p, mxp_se m_total x p")
+    if not (len(chr_ids) == len(snp_ids) == len(ref_alleles) == m_total) or len(trait_names) != p:
+        raise ValueError("one chr / snp / ref entry per mxp row and one name per trait are needed")
+
+    def strings(v):
+        return (C.c_char_p * len(v))(*[str(x).encode() for x in v])
+
+    err = C.create_string_buffer(512)
+    rc = lib().cusk_sumstats_write_se_values(str(outdir).encode(), _ptr(mxp_se), m_total, p, _ptr(pxp_se), strings(chr_ids),
+                                             strings(snp_ids), strings(ref_alleles), strings(trait_names), err, len(err))
+    if rc != 0:
+        raise RuntimeError(f"cusk_sumstats_write_se_values failed ({rc}): {err.value.decode()}")
+
+
+def ordinal_levels(phen, ord_ix):
+    """levels (q x 8 float32, ascending, unused ones 0) and their numbers (q int32) of the ordinal traits `ord_ix` (rows of
+    phen, p x N): the sorted distinct non-NaN values, as `sumstats --ordinal` takes them"""
+    phen = np.asarray(phen, np.float32)
+    levels, nlev = np.zeros((len(ord_ix), 8), np.float32), np.zeros(len(ord_ix), np.int32)
+    for t, ix in enumerate(ord_ix):
+        v = np.unique(phen[ix][~np.isnan(phen[ix])])
+        if not 1 <= len(v) <= 8:
+            raise ValueError(f"trait {ix} has {len(v)} distinct values; an ordinal trait has 1 to 8")
+        levels[t, :len(v)], nlev[t] = v, len(v)
+    return levels, nlev
+
+
 @dataclass
 class Stats:
     level: int
@@ -453,6 +488,80 @@ class Engine:
         mxp_n, pxp_n = np.zeros((k, int(p)), np.int32), np.zeros((int(p), int(p)), np.int32)
         self._check(lib().cusk_pair_counts(self.h, bed_p, phen_p, _ptr(ix), k, m_total, int(N), int(p), _ptr(mxp_n), _ptr(pxp_n)))
         return mxp_n, pxp_n
+
+    def ordinal_tables(self, bed, phen, N: int, p: int, ord_ix, levels, nlev, k: int | None = None, marker_ix=None,
+                       m_total: int | None = None, want_mxo: bool = True):
+        """cusk_ordinal_tables -> (mxo k x q x 3 x 8, oxo q x q x 8 x 8) int32 contingency tables of the ordinal traits
+        `ord_ix` (rows of phen) with the genotype classes of the markers and with one another; levels / nlev as
+        `ordinal_levels` gives them.  bed / phen, k, marker_ix, m_total as `pair_counts` takes them; want_mxo=False
+        counts the trait tables only (bed may then be None)"""
+        clb = (int(N) + 3) // 4
+        ord_ix = np.ascontiguousarray(ord_ix, np.int32)
+        levels = np.ascontiguousarray(levels, np.float32).reshape(len(ord_ix), 8)
+        nlev = np.ascontiguousarray(nlev, np.int32)
+        q = len(ord_ix)
+        if isinstance(phen, DeviceArray):
+            phen_p = phen.ptr
+        else:
+            phen = np.ascontiguousarray(phen, np.float32)
+            phen_p = _ptr(phen)
+        mxo, ix, bed_p = None, None, None
+        if want_mxo:
+            if isinstance(bed, DeviceArray):
+                bed_p, rows = bed.ptr, bed.nbytes // clb
+            else:
+                bed = np.ascontiguousarray(bed, np.uint8)
+                bed_p, rows = _ptr(bed), bed.size // clb
+            m_total = int(rows if m_total is None else m_total)
+            ix = np.ascontiguousarray(marker_ix, np.int32) if marker_ix is not None else None
+            k = int(len(ix) if ix is not None else (m_total if k is None else k))
+            mxo = np.zeros((k, q, 3, 8), np.int32)
+        else:
+            k, m_total = 0, 0
+        oxo = np.zeros((q, q, 8, 8), np.int32)
+        self._check(lib().cusk_ordinal_tables(self.h, bed_p, phen_p, _ptr(ix), k, m_total, int(N), int(p), _ptr(ord_ix), q,
+                                              _ptr(levels), _ptr(nlev), _ptr(mxo), _ptr(oxo)))
+        return mxo, oxo
+
+    def polychoric_fit(self, tables, ka: int | None = None, kb: int | None = None, ntab: int | None = None):
+        """cusk_polychoric_fit -> (r float64, se float64, status int32), one entry per table.  tables: an int32 array whose
+        last two axes are a table (ka x kb, at most 8 x 8), or a DeviceArray with ka, kb and ntab given.  status: 0 fitted,
+        1 boundary (se NaN), 2 degenerate (r and se NaN)"""
+        if isinstance(tables, DeviceArray):
+            tab_p, shape = tables.ptr, (int(ntab),)
+        else:
+            tables = np.ascontiguousarray(tables, np.int32)
+            ka, kb = tables.shape[-2:]
+            shape = tables.shape[:-2]
+            ntab, tab_p = int(np.prod(shape, dtype=np.int64)), _ptr(tables)
+        r, se, status = np.zeros(ntab, np.float64), np.zeros(ntab, np.float64), np.zeros(ntab, np.int32)
+        self._check(lib().cusk_polychoric_fit(self.h, tab_p, int(ntab), int(ka), int(kb), _ptr(r), _ptr(se), _ptr(status)))
+        return r.reshape(shape), se.reshape(shape), status.reshape(shape)
+
+    def polyserial_fit(self, phen, N: int, p: int, cont_ix, ord_ix, levels, nlev):
+        """cusk_polyserial_fit -> (r, se, status), each len(cont_ix) x len(ord_ix): the two-step polyserial correlation of
+        every continuous trait `cont_ix` with every ordinal trait `ord_ix` (rows of phen, host array or DeviceArray) on
+        the pair's complete observations"""
+        cont_ix = np.ascontiguousarray(cont_ix, np.int32)
+        ord_ix = np.ascontiguousarray(ord_ix, np.int32)
+        levels = np.ascontiguousarray(levels, np.float32).reshape(len(ord_ix), 8)
+        nlev = np.ascontiguousarray(nlev, np.int32)
+        if isinstance(phen, DeviceArray):
+            phen_p = phen.ptr
+        else:
+            phen = np.ascontiguousarray(phen, np.float32)
+            phen_p = _ptr(phen)
+        shape = (len(cont_ix), len(ord_ix))
+        r, se, status = np.zeros(shape, np.float64), np.zeros(shape, np.float64), np.zeros(shape, np.int32)
+        self._check(lib().cusk_polyserial_fit(self.h, phen_p, int(N), int(p), _ptr(cont_ix), len(cont_ix), _ptr(ord_ix),
+                                              len(ord_ix), _ptr(levels), _ptr(nlev), _ptr(r), _ptr(se), _ptr(status)))
+        return r, se, status
+
+    def ordinal_timing(self):
+        """cusk_ordinal_timing -> kernel ms of the last ordinal_tables (marker tables), polychoric_fit, polyserial_fit"""
+        ms = np.zeros(3, np.float32)
+        lib().cusk_ordinal_timing(self.h, _ptr(ms))
+        return tuple(float(v) for v in ms)
 
     def marker_pair_sizes(self, bed, N: int, N_dev: int, ld: int, k: int | None = None, marker_ix=None,
                           m_total: int | None = None) -> None:

@@ -401,6 +401,51 @@ float cusk_se_from_count(float r, int count);
 int cusk_sumstats_write_se(const char *outdir, const float *mxp, const int *mxp_n, size_t m_total, size_t p,
                            const float *pxp_square, const int *pxp_n, const char *const *chr, const char *const *snp,
                            const char *const *ref, const char *const *trait_names, char *err, size_t err_len);
+/* Host only.  mxp_se.txt / pxp_se.txt as cusk_sumstats_write_se writes them, from finished standard errors (mxp_se m_total x
+ * p, pxp_se p x p) instead of counts: the polychoric / polyserial standard errors of ordinal traits do not come from a
+ * count.  NaN goes out as NA in mxp_se and nan in pxp_se; the caller puts NaN on the diagonal of pxp_se. */
+int cusk_sumstats_write_se_values(const char *outdir, const float *mxp_se, size_t m_total, size_t p, const float *pxp_se,
+                                  const char *const *chr, const char *const *snp, const char *const *ref,
+                                  const char *const *trait_names, char *err, size_t err_len);
+/* Contingency tables of ordinal traits, counted on the device: the input of cusk_polychoric_fit.  The q ordinal traits are
+ * the rows ord_ix[0 .. q-1] (0-based, HOST) of phen (p x N, trait-major, host or device-resident); trait t has the nlev[t]
+ * (1 .. 8) levels levels[t * 8 + 0 .. nlev[t] - 1] (HOST, ascending), which must hold every distinct non-NaN value of the
+ * trait: an individual whose value is none of them is in no table.  A marker has the three genotype classes of its
+ * non-missing .bed codes in the order of the dosage the Pearson build gives them (code 11 -> class 0, 10 -> 1, 00 -> 2).
+ *   mxo_tab_host[((i * q + t) * 3 + c) * 8 + u]   individuals with class c of marker i and level u of ordinal trait t
+ *   oxo_tab_host[((a * q + b) * 8 + u) * 8 + v]   individuals with level u of ordinal trait a and level v of ordinal trait b
+ * k * q * 3 * 8 and q * q * 8 * 8 int32; cells of levels a trait does not have are 0.  Markers, bed, marker_ix, k, m_total
+ * and N as cusk_pair_counts takes them, with its guarantees: rows start at any byte, individuals are 0 .. N-1 whatever the
+ * last byte of a row or the memory behind it holds, counts are exact.  Either output may be NULL (bed may then be NULL
+ * when mxo_tab_host is).  Returns when the tables are there. */
+int cusk_ordinal_tables(cusk_engine *e, const unsigned char *bed, const float *phen, const int *marker_ix, size_t k,
+                        size_t m_total, size_t N, size_t p, const int *ord_ix, size_t q, const float *levels, const int *nlev,
+                        int *mxo_tab_host, int *oxo_tab_host);
+/* Polychoric correlations (polycor's two-step form) of ntab contingency tables of ka x kb int32 counts each (ka, kb <= 8;
+ * host memory, or device-resident and read in place), one fit per table on the device, in IEEE double: rows and columns
+ * without observations are left out; thresholds are the normal quantiles of the cumulative shares; rho maximises
+ * sum n_ab log pi_ab(rho) over [-0.9999, 0.9999] with the thresholds held fixed (bivariate normal rectangle probabilities by
+ * Genz's algorithm); se = 1 / sqrt(-l''(rho)).  status_out: 0 fitted; 1 boundary -- rho is +-0.9999, or the information is
+ * not positive: r is set, se is NaN; 2 degenerate -- a side has fewer than two levels with observations: r and se are NaN.
+ * r_out, se_out (double) and status_out (int): ntab values each, HOST.  Returns when they are there. */
+int cusk_polychoric_fit(cusk_engine *e, const int *tables, size_t ntab, int ka, int kb, double *r_out, double *se_out,
+                        int *status_out);
+/* Polyserial correlations (two-step) of the continuous traits cont_ix[0 .. nc-1] with the ordinal traits ord_ix[0 .. q-1]
+ * (trait indices into phen, p x N, host or device-resident; levels / nlev as cusk_ordinal_tables takes them), each pair on
+ * the individuals for which neither value is NaN: z = (x - mean) / sd (n - 1), thresholds from the ordinal trait's
+ * cumulative shares, rho maximises sum_i log[Phi((tau_hi - rho z_i) / sqrt(1 - rho^2)) - Phi((tau_lo - rho z_i) / sqrt(1 -
+ * rho^2))]; an individual whose ordinal value is none of the listed levels is left out, as in cusk_ordinal_tables;
+ * interval, se and status as cusk_polychoric_fit (degenerate also: fewer than two observations, or a constant
+ * x).  Outputs: nc * q values each, pair (c, o) at c * q + o, HOST.  Sums over individuals are formed in a fixed order.
+ * Returns when they are there. */
+int cusk_polyserial_fit(cusk_engine *e, const float *phen, size_t N, size_t p, const int *cont_ix, size_t nc, const int *ord_ix,
+                        size_t q, const float *levels, const int *nlev, double *r_out, double *se_out, int *status_out);
+/* M_dev[idx * n + j] = M_dev[j * n + idx] = vals_host[j] for j < n: one variable's row and column of a device-resident n x n
+ * matrix replaced from a host vector (the ordinal traits' correlations and sample sizes in `mps cuskss-bed ... het
+ * ordinal=`).  Returns when the matrix is written. */
+int cusk_matrix_set_cross(cusk_engine *e, float *M_dev, size_t n, size_t idx, const float *vals_host);
+/* kernel times of the last calls (ms): [0] table kernel of cusk_ordinal_tables, [1] cusk_polychoric_fit, [2] cusk_polyserial_fit */
+void cusk_ordinal_timing(const cusk_engine *e, float *ms3);
 /* timing of the last cusk_corr_build: [0] decode, [1] count GEMM, [2] mxp/pxp, [3] total (ms) */
 void cusk_corr_timing(const cusk_engine *e, float *ms4);
 
