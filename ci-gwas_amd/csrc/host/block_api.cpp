@@ -129,18 +129,8 @@ extern "C" int cusk_blockset_stage(cusk_blockset *bs, cusk_engine *e)
     const CuskInputs &in = bs->in;
     const size_t bed_bytes = in.bed.size > 3 ? in.bed.size - 3 : 0, pad = 4096;
     StagedInputs st;
-    st.bed = static_cast<unsigned char *>(cusk_dev_alloc(bed_bytes + pad));
-    st.phen = static_cast<float *>(cusk_dev_alloc(sizeof(float) * in.phen.data.size() + pad));
-    st.means = static_cast<float *>(cusk_dev_alloc(sizeof(float) * in.means_all.size() + pad));
-    st.stds = static_cast<float *>(cusk_dev_alloc(sizeof(float) * in.stds_all.size() + pad));
-    bool ok = st.bed && st.phen && st.means && st.stds;
-    ok = ok && cusk_dev_upload(st.bed, in.bed.data + 3, bed_bytes) == CUSK_OK;
-    ok = ok && cusk_dev_upload(st.phen, in.phen.data.data(), sizeof(float) * in.phen.data.size()) == CUSK_OK;
-    ok = ok && cusk_dev_upload(st.means, in.means_all.data(), sizeof(float) * in.means_all.size()) == CUSK_OK;
-    ok = ok && cusk_dev_upload(st.stds, in.stds_all.data(), sizeof(float) * in.stds_all.size()) == CUSK_OK;
-    if (!ok)
+    if (stage_inputs(st, in.bed.data + 3, bed_bytes, in.phen.data, in.means_all, in.stds_all, pad, nullptr))
     {
-        st.release();
         copy_err("staging the block set's inputs on the device failed (not enough device memory?)", nullptr, 0);
         return CUSK_ERR_HIP;
     }

@@ -18,7 +18,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "block_pipeline.h"
+#include "host_io.h"
 
 namespace host {
 

@@ -20,6 +20,13 @@ struct OrdinalSpec
     size_t q() const { return ix.size(); }
 };
 
+// Polychoric / polyserial estimates of every pair of a trait with an ordinal trait, as float32 the files hold: r and se
+// are formed in double on the device and rounded once (ordinal_estimates.h).
+struct OrdinalTraitEstimates
+{
+    std::vector<float> r, se;  // p x q: trait a with ordinal trait spec.ix[t]; its own entry is not set
+};
+
 // "ordinal=2,5" -> {1, 4}; every error is a std::runtime_error with a message for the user
 inline std::vector<int> parse_ordinal_arg(const std::string &arg, size_t num_phen)
 {

@@ -79,6 +79,11 @@ def cu_corr_pearson_npn(bed, phen, m, N, p, means, stds):
     return mxm[: m * (m - 1) // 2], mxp[: m * p], pxp[: p * (p - 1) // 2]
 
 
+def _strings(v):
+    """a sequence of names as the `const char *const *` the writers take"""
+    return (C.c_char_p * len(v))(*[str(x).encode() for x in v])
+
+
 def sumstats_write(outdir: str, mxm_tri, mxp, pxp, chr_ids, snp_ids, ref_alleles, trait_names) -> None:
     """cusk_sumstats_write (host only): <outdir>/mxm.bin, mxp.txt, pxp.txt from arrays -- mxm_tri the lower triangle
     with diagonal of the selected markers' LD, mxp m_total x p for every marker of the .bim, pxp p x p"""
@@ -93,12 +98,9 @@ def sumstats_write(outdir: str, mxm_tri, mxp, pxp, chr_ids, snp_ids, ref_alleles
     if not (len(chr_ids) == len(snp_ids) == len(ref_alleles) == m_total) or len(trait_names) != p:
         raise ValueError("one chr / snp / ref entry per mxp row and one name per trait are needed")
 
-    def strings(v):
-        return (C.c_char_p * len(v))(*[str(x).encode() for x in v])
-
     err = C.create_string_buffer(512)
-    rc = lib().cusk_sumstats_write(str(outdir).encode(), _ptr(tri), k, _ptr(mxp), m_total, p, _ptr(pxp), strings(chr_ids),
-                                   strings(snp_ids), strings(ref_alleles), strings(trait_names), err, len(err))
+    rc = lib().cusk_sumstats_write(str(outdir).encode(), _ptr(tri), k, _ptr(mxp), m_total, p, _ptr(pxp), _strings(chr_ids),
+                                   _strings(snp_ids), _strings(ref_alleles), _strings(trait_names), err, len(err))
     if rc != 0:
         raise RuntimeError(f"cusk_sumstats_write failed ({rc}): {err.value.decode()}")
 
@@ -145,12 +147,9 @@ def sumstats_write_se(outdir: str, mxp, mxp_n, pxp, pxp_n, chr_ids, snp_ids, ref
     if not (len(chr_ids) == len(snp_ids) == len(ref_alleles) == m_total) or len(trait_names) != p:
         raise ValueError("one chr / snp / ref entry per mxp row and one name per trait are needed")
 
-    def strings(v):
-        return (C.c_char_p * len(v))(*[str(x).encode() for x in v])
-
     err = C.create_string_buffer(512)
     rc = lib().cusk_sumstats_write_se(str(outdir).encode(), _ptr(mxp), _ptr(mxp_n), m_total, p, _ptr(pxp), _ptr(pxp_n),
-                                      strings(chr_ids), strings(snp_ids), strings(ref_alleles), strings(trait_names), err, len(err))
+                                      _strings(chr_ids), _strings(snp_ids), _strings(ref_alleles), _strings(trait_names), err, len(err))
     if rc != 0:
         raise RuntimeError(f"cusk_sumstats_write_se failed ({rc}): {err.value.decode()}")
 
@@ -167,12 +166,9 @@ def sumstats_write_se_values(outdir: str, mxp_se, pxp_se, chr_ids, snp_ids, ref_
     if not (len(chr_ids) == len(snp_ids) == len(ref_alleles) == m_total) or len(trait_names) != p:
         raise ValueError("one chr / snp / ref entry per mxp row and one name per trait are needed")
 
-    def strings(v):
-        return (C.c_char_p * len(v))(*[str(x).encode() for x in v])
-
     err = C.create_string_buffer(512)
-    rc = lib().cusk_sumstats_write_se_values(str(outdir).encode(), _ptr(mxp_se), m_total, p, _ptr(pxp_se), strings(chr_ids),
-                                             strings(snp_ids), strings(ref_alleles), strings(trait_names), err, len(err))
+    rc = lib().cusk_sumstats_write_se_values(str(outdir).encode(), _ptr(mxp_se), m_total, p, _ptr(pxp_se), _strings(chr_ids),
+                                             _strings(snp_ids), _strings(ref_alleles), _strings(trait_names), err, len(err))
     if rc != 0:
         raise RuntimeError(f"cusk_sumstats_write_se_values failed ({rc}): {err.value.decode()}")
 
