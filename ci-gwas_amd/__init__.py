@@ -20,6 +20,8 @@ from .skeleton import (  # noqa: F401
     hetcor_skeleton,
     hetcor_threshold,
     ordinal_levels,
+    phen_table_load,
+    phen_write,
     prune_write,
     se_from_count,
     sumstats_write,

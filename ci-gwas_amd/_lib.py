@@ -145,6 +145,19 @@ SYMBOLS = {
     "cusk_ld_prune": (_i, [_vp, _vp, _sz, _sz, _sz, _f, _vp, _vp]),
     "cusk_ld_prune_timing": (None, [_vp, _vp]),
     "cusk_prune_write": (_i, [C.c_char_p, C.c_char_p, _vp, _sz]),
+    "cusk_phen_adjust": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cusk_phen_moments": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "cusk_phen_timing": (None, [_vp, _vp]),
+    "cusk_phen_table_load": (_i, [C.POINTER(_vp), C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
+    "cusk_phen_table_rows": (_sz, [_vp]),
+    "cusk_phen_table_cols": (_sz, [_vp]),
+    "cusk_phen_table_name": (C.c_char_p, [_vp, _sz]),
+    "cusk_phen_table_data": (_vp, [_vp]),
+    "cusk_phen_table_matched": (_sz, [_vp]),
+    "cusk_phen_table_dropped": (_sz, [_vp]),
+    "cusk_phen_table_in_order": (_i, [_vp]),
+    "cusk_phen_table_free": (None, [_vp]),
+    "cusk_phen_write": (_i, [C.c_char_p, C.c_char_p, _vp, _sz, _vp, _sz, C.c_char_p, _sz]),
     "cusk_sepselect_greedy": (_i, [_vp, _vp, C.c_longlong, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "cusk_sepselect_greedy_het": (_i, [_vp, _vp, C.c_longlong, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
     "cusk_iv_check": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -7,11 +7,18 @@ positional / optional arguments, same range checks, same conversion to the posit
 the native `mps` program with literal 'NULL' for absent paths, `subprocess.run(check=True)`.
 `cuskss-het` and `cuskss-merged` (README.md:65,75 of the reference names them, its CLI does
 not define them) are aliases of `cuskss` that insist on the flags that select that mode.
-The workflow is prune-bed -> prep-bed -> block -> cusk -> merge-block-outputs -> cuskss-merged -> sepselect -> check-ivs.
+The workflow is prune-bed -> prep-bed -> prep-phen -> block -> cusk -> merge-block-outputs -> cuskss-merged -> sepselect ->
+check-ivs.
 `prune-bed` is not in the reference: its README asks for a fileset that is LD pruned ("or at least does not have markers
 with a correlation of 1") and has no marker without recorded variation, and leaves both to the user.  Here they are
 decided on the device, on the banded Kendall-npn correlation that `block` and the skeleton use (`mps prune`): markers in
 .bim order per chromosome, the first kept marker wins.  That is not PLINK's rule (Pearson r^2, higher MAF kept).
+`prep-phen` is not in the reference either: its README warns "make sure that the trait values are standardized" and its
+loader takes the rows of the .phen as they come.  `prep-phen BFILES TABLE OUT [--covar FILE] [--ordinal NAMES]` matches a
+trait table to the .fam by IID, removes the covariates from every trait by least squares (never from an ordinal one: a
+residual has no levels) and standardises to mean 0 and population sd 1 over the observed values, on the device (`mps
+prep-phen`; the rule is stated in include/cusk_hip.h).  `check-phen BFILES PHEN` reports whether an existing .phen is
+row-aligned and standardised and exits 1 if not.
 Two more things the reference leaves to the user: `sumstats` writes the three correlation files of `cuskss` from a
 PLINK set and a .phen, and `cuskss-merged --bfiles --phen` runs the merged step straight from those.  For phenotypes
 with missing values `sumstats --se` adds the two standard-error files (from the number of individuals each pair was
@@ -109,6 +116,29 @@ def _add_prune(sub):
     p.add_argument("--window", type=TypeCheck(int, "window", 1, 4096), default=2000,
                    help="number of following markers each marker is compared with (default: the corr-width of block)")
     p.set_defaults(func=prune_bed)
+
+
+def _add_prep_phen(sub):
+    """not in ci-gwas.py: the reference's README leaves standardised traits to the user (cusk/scripts/phen_prep.py checks)"""
+    p = sub.add_parser("prep-phen", help="Match a trait table to the .fam by IID, remove covariates from the traits and "
+                                         "standardise them; goes in front of cusk / sumstats (requires GPU)")
+    p.add_argument("bfiles", type=str, help="filestem of .bed, .bim, .fam fileset (the .fam is read)")
+    p.add_argument("table", type=str, help="trait table: header FID IID <traits> (ids in either order, IID may be EID), NA = missing")
+    p.add_argument("out", type=str, help="the .phen to write (one row per individual of the .fam, in its order); also "
+                                         "receives <out>.prep.tsv with n, mean, sd and r2 per trait")
+    p.add_argument("--covar", type=str, default=None, metavar="FILE",
+                   help="covariate table in the format of the trait table (at most 63 numeric columns; dummy-code categories): "
+                        "every trait is regressed on them, with an intercept, over the individuals that have the trait and "
+                        "every covariate")
+    p.add_argument("--ordinal", type=str, default=None, metavar="NAMES",
+                   help="comma-separated names (or 1-based numbers) of the traits that are ordinal, as `sumstats --ordinal` "
+                        "takes them: standardised only, never residualised (a residual has no levels)")
+    p.set_defaults(func=prep_phen)
+    p = sub.add_parser("check-phen", help="Report whether a .phen is row-aligned to the .fam and standardised; exit status 1 "
+                                          "if not (requires GPU)")
+    p.add_argument("bfiles", type=str, help="filestem of .bed, .bim, .fam fileset (the .fam is read)")
+    p.add_argument("phen", type=str, help="path to phenotype tsv")
+    p.set_defaults(func=check_phen)
 
 
 def _add_block(sub):
@@ -239,6 +269,7 @@ def build_parser() -> argparse.ArgumentParser:
     sub = parser.add_subparsers(required=True, title="subcommands")
     _add_prune(sub)
     _add_prep(sub)
+    _add_prep_phen(sub)
     _add_block(sub)
     _add_cusk(sub)
     _add_cuskss(sub, "cuskss", "Infer skeleton using summary statistic data (requires GPU)")
@@ -356,6 +387,38 @@ def sumstats_argv(args) -> list[str]:
 
 def sumstats(args):
     subprocess.run(sumstats_argv(args), check=True)
+
+
+def _same_path(a: str, b: str) -> bool:
+    return a == b or (os.path.exists(a) and os.path.exists(b) and os.path.samefile(a, b))
+
+
+def prep_phen_argv(args) -> list[str]:
+    """`mps prep-phen <bfiles> <table> <out> <covar|NULL> [ordinal=<1-based,...>]`"""
+    covar = getattr(args, "covar", None)
+    if _same_path(args.out, args.table):
+        sys.exit("prep-phen: OUT must differ from TABLE.")
+    if covar is not None and _same_path(args.out, covar):
+        sys.exit("prep-phen: OUT must differ from the --covar file.")
+    if _same_path(args.out, args.bfiles + ".fam"):
+        sys.exit("prep-phen: OUT must differ from the .fam.")
+    ordinal = getattr(args, "ordinal", None)
+    return [MPS_PATH, "prep-phen", args.bfiles, args.table, args.out, covar if covar is not None else "NULL"] + (
+        [ordinal_arg("prep-phen", ordinal, args.table)] if ordinal is not None else [])
+
+
+def check_phen_argv(args) -> list[str]:
+    """`mps check-phen <bfiles> <phen>`"""
+    return [MPS_PATH, "check-phen", args.bfiles, args.phen]
+
+
+def prep_phen(args):
+    subprocess.run(prep_phen_argv(args), check=True)
+
+
+def check_phen(args):
+    """exit status 1 (and one line per failing trait on stdout) when the .phen is not row-aligned and standardised"""
+    sys.exit(subprocess.run(check_phen_argv(args)).returncode)
 
 
 def cuskss_bed_argv(args) -> list[str]:

@@ -211,6 +211,7 @@ struct cusk_engine
     float prune_ms[5] = {0, 0, 0, 0, 0};  // cusk_ld_prune_timing: upload, band, counts, bitmap, scan of the last cusk_ld_prune
     float ord_ms[3] = {0, 0, 0};  // cusk_ordinal_timing: table kernel, polychoric fit kernel, polyserial fit kernel of their last calls
     hipEvent_t ev_prune[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // its phase marks, created by the first cusk_ld_prune
+    float phen_ms[5] = {0, 0, 0, 0, 0};  // cusk_phen_timing: scaling, Gram, solve, moments, standardise of the last cusk_phen_adjust
 };
 
 namespace cusk {

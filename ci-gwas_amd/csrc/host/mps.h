@@ -15,6 +15,8 @@ int cmd_cuskss_bed(int argc, char **argv);
 int cmd_block(int argc, char **argv);
 int cmd_prune(int argc, char **argv);
 int cmd_prep(int argc, char **argv);
+int cmd_prep_phen(int argc, char **argv);
+int cmd_check_phen(int argc, char **argv);
 
 // wall-clock phase marks, printed as "[t] <phase>: <ms> ms" when CUSK_TIMING is set (tools/e2e_block.py)
 struct PhaseTimer

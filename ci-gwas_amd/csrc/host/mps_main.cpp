@@ -8,10 +8,12 @@
 //   mps cusk   <.phen> <bfiles> <.blocks> <alpha> <max-level> <max-level-two> <depth> <outdir> <block-index> [het] [filter] [rows] [markers]
 //   mps cuskss <mxm> <mxp> <mxp_se> <pxp> <pxp_se> <time_index> <block_index> <blockfile>
 //              <marker_indices> <alpha> <l1> <l2> <depth> <num_samples> <outdir>   ("NULL" = absent)
-// and three commands the reference does not have:
+// and five commands the reference does not have:
 //   mps sumstats   <.phen> <bfiles> <marker-indices|NULL> <outdir> [se] [ordinal=<1-based,...>]
 //   mps cuskss-bed <.phen> <bfiles> <marker-indices> <time_index|NULL> <alpha> <l1> <l2> <depth> <outdir> [het] [markers] [ordinal=<1-based,...>]
 //   mps prune      <bfiles> <out-stem> <r-max> <window>
+//   mps prep-phen  <bfiles> <table> <out> <covar|NULL> [ordinal=<1-based,...>]
+//   mps check-phen <bfiles> <.phen>
 // Differences by design: the correlation matrix never leaves HBM between the build and the
 // sweep, adjacency comes back as a bitmap, separating sets as sparse records, only the
 // retained sub-matrix is gathered to the host, and files are written with one fwrite each.
@@ -37,6 +39,8 @@ commands:
     block                   Tile the marker x marker correlation matrix of every chromosome into LD blocks
     prep                    Prepare input (PLINK) .bed file for cusk: .dim, .means, .stds, .modes
     prune                   Drop constant markers and LD-prune a fileset (goes in front of prep)
+    prep-phen               Match a trait table to the .fam, remove covariates from the traits and standardise them
+    check-phen              Check that a .phen is row-aligned to the .fam and standardised (status 1 if not)
 )";
 
 }  // namespace
@@ -58,6 +62,8 @@ int main(int argc, char **argv)
         if (cmd == "block") return cmd_block(argc, argv);
         if (cmd == "prep") return cmd_prep(argc, argv);
         if (cmd == "prune") return cmd_prune(argc, argv);
+        if (cmd == "prep-phen") return cmd_prep_phen(argc, argv);
+        if (cmd == "check-phen") return cmd_check_phen(argc, argv);
     }
     catch (const Fatal &f)
     {  // bad input: message + status 1, as the reference's loaders and argument checks do (cli.cpp:185-192)

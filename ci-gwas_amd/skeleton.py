@@ -133,6 +133,43 @@ def prune_write(bfiles: str, out_stem: str, status) -> None:
         raise RuntimeError(f"cusk_prune_write failed ({rc}): see stderr")
 
 
+def phen_table_load(table_path: str, fam_path: str | None = None):
+    """cusk_phen_table_load (host only) -> (names, data cols x N float32 trait-major, info): a trait or covariate table,
+    matched by IID to the individuals of `fam_path` in its order (absent individuals NaN, rows the .fam does not list
+    dropped), or with its rows as they come.  info: matched, dropped, in_order.  Raises ValueError with the loader's message
+    (line and column of a bad token, a duplicate IID, a ragged row, a header without FID / IID)."""
+    h, err = C.c_void_p(), C.create_string_buffer(1024)
+    rc = lib().cusk_phen_table_load(C.byref(h), str(table_path).encode(), str(fam_path).encode() if fam_path is not None else None,
+                                    err, len(err))
+    if rc != 0:
+        raise ValueError(err.value.decode())
+    try:
+        L = lib()
+        N, p = int(L.cusk_phen_table_rows(h)), int(L.cusk_phen_table_cols(h))
+        names = [L.cusk_phen_table_name(h, j).decode() for j in range(p)]
+        data = np.empty((p, N), np.float32)
+        if data.size:
+            C.memmove(_ptr(data), L.cusk_phen_table_data(h), data.nbytes)
+        info = {"matched": int(L.cusk_phen_table_matched(h)), "dropped": int(L.cusk_phen_table_dropped(h)),
+                "in_order": bool(L.cusk_phen_table_in_order(h))}
+    finally:
+        lib().cusk_phen_table_free(h)
+    return names, data, info
+
+
+def phen_write(path: str, fam_path: str, names, data) -> None:
+    """cusk_phen_write (host only): a .phen for the individuals of `fam_path` in its order; data p x N float32 trait-major,
+    NaN goes out as NA"""
+    data = np.ascontiguousarray(data, np.float32)
+    if data.ndim != 2 or data.shape[0] != len(names):
+        raise ValueError("data must be len(names) x N")
+    arr = (C.c_char_p * len(names))(*[str(s).encode() for s in names])
+    err = C.create_string_buffer(1024)
+    rc = lib().cusk_phen_write(str(path).encode(), str(fam_path).encode(), arr, len(names), _ptr(data), data.shape[1], err, len(err))
+    if rc != 0:
+        raise RuntimeError(f"cusk_phen_write failed ({rc}): {err.value.decode()}")
+
+
 def sumstats_write_se(outdir: str, mxp, mxp_n, pxp, pxp_n, chr_ids, snp_ids, ref_alleles, trait_names) -> None:
     """cusk_sumstats_write_se (host only): <outdir>/mxp_se.txt, pxp_se.txt from the correlations sumstats_write wrote and
     the per-pair observation counts of Engine.pair_counts (mxp_n m_total x p, pxp_n p x p)"""
@@ -484,6 +521,59 @@ class Engine:
         mxp_n, pxp_n = np.zeros((k, int(p)), np.int32), np.zeros((int(p), int(p)), np.int32)
         self._check(lib().cusk_pair_counts(self.h, bed_p, phen_p, _ptr(ix), k, m_total, int(N), int(p), _ptr(mxp_n), _ptr(pxp_n)))
         return mxp_n, pxp_n
+
+    def phen_moments(self, phen, N: int, p: int):
+        """cusk_phen_moments -> (n int32, mean, sd float64) per trait over its finite values (population sd); phen p x N
+        trait-major, a host array or a DeviceArray"""
+        if isinstance(phen, DeviceArray):
+            phen_p = phen.ptr
+        else:
+            phen = np.ascontiguousarray(phen, np.float32)
+            phen_p = _ptr(phen)
+        n, mean, sd = np.zeros(int(p), np.int32), np.zeros(int(p)), np.zeros(int(p))
+        self._check(lib().cusk_phen_moments(self.h, phen_p, int(N), int(p), _ptr(n), _ptr(mean), _ptr(sd)))
+        return n, mean, sd
+
+    def phen_adjust(self, phen, covar, N: int, p: int, c: int, adjust=None, out=None, stats=None):
+        """cusk_phen_adjust -> dict(out p x N float32, n, mean, sd, beta p x (c + 1), r2, status): every trait residualised
+        on the c covariates (where adjust[t], default all) and standardised to mean 0 and population sd 1 over its observed
+        values; the rule is stated in include/cusk_hip.h.  phen p x N and covar c x N float32, NaN = missing, host arrays
+        or DeviceArray copies.  `out` (p * N float32 at its start) and `stats` (dict of preallocated n / mean / sd / beta /
+        r2 / status arrays) let a caller put guards behind the results."""
+        N, p, c = int(N), int(p), int(c)
+        if isinstance(phen, DeviceArray):
+            phen_p = phen.ptr
+        else:
+            phen = np.ascontiguousarray(phen, np.float32)
+            phen_p = _ptr(phen)
+        if covar is None:
+            covar_p = None
+        elif isinstance(covar, DeviceArray):
+            covar_p = covar.ptr
+        else:
+            covar = np.ascontiguousarray(covar, np.float32)
+            covar_p = _ptr(covar)
+        adjust = np.ones(p, np.uint8) if adjust is None else np.ascontiguousarray(adjust, np.uint8)
+        if adjust.size != p:
+            raise ValueError("one adjust flag per trait is needed")
+        stats = dict(stats or {})
+        res = {"out": np.empty(p * N, np.float32) if out is None else out,
+               "n": stats.get("n", np.zeros(p, np.int32)), "mean": stats.get("mean", np.zeros(p)), "sd": stats.get("sd", np.zeros(p)),
+               "beta": stats.get("beta", np.zeros(p * (c + 1))), "r2": stats.get("r2", np.zeros(p)),
+               "status": stats.get("status", np.zeros(p, np.int32))}
+        self._check(lib().cusk_phen_adjust(self.h, phen_p, covar_p, N, p, c, _ptr(adjust), _ptr(res["out"]), _ptr(res["n"]),
+                                           _ptr(res["mean"]), _ptr(res["sd"]), _ptr(res["beta"]), _ptr(res["r2"]), _ptr(res["status"])))
+        res["out"] = res["out"][:p * N].reshape(p, N)
+        res["beta"] = res["beta"][:p * (c + 1)].reshape(p, c + 1)
+        for key in ("n", "mean", "sd", "r2", "status"):
+            res[key] = res[key][:p]
+        return res
+
+    def phen_timing(self):
+        """cusk_phen_timing: ms of scaling, Gram, solve, moments, standardise in the last phen_adjust"""
+        ms = np.zeros(5, np.float32)
+        lib().cusk_phen_timing(self.h, _ptr(ms))
+        return ms
 
     def ordinal_tables(self, bed, phen, N: int, p: int, ord_ix, levels, nlev, k: int | None = None, marker_ix=None,
                        m_total: int | None = None, want_mxo: bool = True):

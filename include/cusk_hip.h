@@ -523,6 +523,80 @@ void cusk_ld_prune_timing(const cusk_engine *e, float *ms5);
  * never).  The reason goes to stderr. */
 int cusk_prune_write(const char *bfiles, const char *out_stem, const unsigned char *status, size_t m_total);
 
+/* `prep-phen`: traits residualised on covariates and standardised, on the device (phen_adjust.hip).  The third precondition
+ * the reference's README leaves to the user ("make sure that the trait values are standardized"; its
+ * cusk/scripts/phen_prep.py only checks it): the Pearson kernels form sum(y_a * y_b) / #jointly valid and so assume mean 0
+ * and POPULATION standard deviation 1 (divisor n, not n - 1) of every trait over its observed values -- the quantity
+ * pxp_kernel and the .stds of `mps prep` assume, hence the one used here.
+ * Inputs: Y p x N float32 trait-major, X c x N float32 covariate-major, NaN (or +-Inf) = missing; adjust[t] per trait;
+ * 0 <= c <= CUSK_PHEN_MAX_COVAR (64 columns with the intercept).  All arithmetic is IEEE double; only out is rounded.
+ *   1. A = { i : every X[j, i] is finite }                                     (c == 0: everybody)
+ *   2. per covariate mu_j = mean and sigma_j = population sd over A (two passes), xs = (x - mu_j) / sigma_j.  Residuals do
+ *      not depend on this map in exact arithmetic; it is there so that the normal equations are formed on a well-scaled
+ *      design.  sigma_j == 0 (or A empty): CUSK_ERR_ARG with a message that names j, nothing is written.
+ *   3. adjusted traits (adjust[t] != 0 and c > 0): U_t = A and Y[t, i] finite, n_t = |U_t|, z_i = (1, xs_i),
+ *      G_t = sum_{U_t} z z', b_t = sum_{U_t} z y; beta_t solves G_t beta = b_t by Cholesky on D^-1/2 G_t D^-1/2
+ *      (D = diag G_t, unit diagonal); e_i = y_i - z_i' beta_t, computed from the data, not from G
+ *   4. other traits: U_t = { i : Y[t, i] finite }, e = y
+ *   5. every trait: m = sum(e) / n_t, s = sqrt(sum((e - m)^2) / n_t) (two passes, the second over the centred values);
+ *      out[t, i] = (float)((e_i - m) / s) for i in U_t, NaN elsewhere
+ *   6. status[t]: CUSK_PHEN_OK; CUSK_PHEN_SINGULAR when a pivot of the unit-diagonal factorisation is below
+ *      CUSK_PHEN_PIVOT_MIN (a pivot is 1 - R^2 of a covariate on the earlier ones over U_t: "explained to eight digits by
+ *      the others"; far above the rounding floor c n 2^-53 of a double Gram and far below any design a person would call
+ *      non-collinear; part of the rule, not a knob); CUSK_PHEN_TOO_FEW when n_t < c + 2 (not adjusted: n_t < 2) or s == 0.
+ *      A trait with status != 0 is all NaN in out, and NaN in mean, sd, beta and r2.
+ *   7. every sum over individuals runs over chunks of CUSK_PHEN_CHUNK individuals, in a fixed order inside the chunk; the
+ *      chunk partials are added in chunk order.  No floating-point atomics: two calls on the same input give the same bytes.
+ * Outputs (HOST; out_host p x N, the others per trait; any of n/mean/sd/beta/r2/status may be NULL): n_out = n_t;
+ * mean_out, sd_out = m and s of step 5; beta_out (c + 1) per trait in the units of the RAW covariates, intercept first
+ * (NaN for traits that are not adjusted); r2_out = 1 - sum(e^2) / sum((y - ybar)^2) over U_t (NaN when not adjusted).
+ * phen and covar may each be host memory or device-resident, as cusk_pair_counts takes phen.  Individuals are 0 .. N-1;
+ * nothing behind the arrays is read or written.  CUSK_ERR_ARG (message in cusk_last_error, nothing launched): a null
+ * engine, phen, adjust or out_host, N == 0, p == 0, c > CUSK_PHEN_MAX_COVAR, covar NULL with c > 0, N >= 2^31. */
+#define CUSK_PHEN_MAX_COVAR 63
+#define CUSK_PHEN_CHUNK 4096
+#define CUSK_PHEN_PIVOT_MIN 1e-8
+enum
+{
+    CUSK_PHEN_OK = 0,
+    CUSK_PHEN_SINGULAR = 1,
+    CUSK_PHEN_TOO_FEW = 2
+};
+int cusk_phen_adjust(cusk_engine *e, const float *phen, const float *covar, size_t N, size_t p, size_t c,
+                     const unsigned char *adjust, float *out_host, int *n_out, double *mean_out, double *sd_out,
+                     double *beta_out, double *r2_out, int *status_out);
+/* The moments of step 5 alone on the values as they are (`check-phen`): n, m and s of every trait over its finite values,
+ * with the same chunks and order; n == 0 gives NaN, NaN. */
+int cusk_phen_moments(cusk_engine *e, const float *phen, size_t N, size_t p, int *n_out, double *mean_out, double *sd_out);
+/* HIP-event times of the last cusk_phen_adjust on e: covariate mask and scaling, Gram partials, their ordered sum and the
+ * Cholesky solves, residual moments (both passes), standardise.  ms5: 5 floats. */
+void cusk_phen_timing(cusk_engine *e, float *ms5);
+
+/* Host only.  A trait or covariate table read and aligned to a .fam (host/phen_table.h).  Whitespace-separated text; the
+ * header names two id columns, FID and IID in either order (IID may be called EID), then the value columns; NA tokens are
+ * NA, NaN, nan, NAN; any other token that is not a number is an error with its line and column, as are a row of another
+ * width, a duplicate IID, a header without the id columns and an empty file.  CRLF line ends are accepted; a header alone
+ * is a table without rows.  With fam_path the rows are matched to the .fam (FID IID ...) by IID: the result has one row
+ * per line of the .fam, in its order, individuals of the .fam that the table does not list are NaN in every column, rows of
+ * the table that the .fam does not list are dropped and counted.  Without it (NULL) the rows stand as they come.
+ * On failure: an error code, *out = NULL and the message in err (may be NULL). */
+typedef struct cusk_phen_table cusk_phen_table;
+int cusk_phen_table_load(cusk_phen_table **out, const char *table_path, const char *fam_path, char *err, size_t err_len);
+size_t cusk_phen_table_rows(const cusk_phen_table *t);          /* N: lines of the .fam (rows of the table without one) */
+size_t cusk_phen_table_cols(const cusk_phen_table *t);          /* value columns */
+const char *cusk_phen_table_name(const cusk_phen_table *t, size_t col);
+const float *cusk_phen_table_data(const cusk_phen_table *t);    /* cols x N, column-major (trait-major), NaN = NA */
+size_t cusk_phen_table_matched(const cusk_phen_table *t);       /* individuals of the .fam found in the table */
+size_t cusk_phen_table_dropped(const cusk_phen_table *t);       /* rows of the table the .fam does not list */
+int cusk_phen_table_in_order(const cusk_phen_table *t);         /* 1: as many rows as the .fam and the same IID line by line */
+void cusk_phen_table_free(cusk_phen_table *t);
+/* Host only.  A .phen for the individuals of fam_path, in its order: header "FID\tIID\t<names>", the .fam's own FID and IID,
+ * values %.9g (round-trips float32 through the loader of `mps cusk`), NaN as NA.  data: p x N trait-major, N = lines of the
+ * .fam.  CUSK_ERR_ARG for null pointers, p == 0, a .fam that cannot be read or does not have N lines, a path that names the
+ * .fam; CUSK_ERR_STATE when the file cannot be written in full (it is removed). */
+int cusk_phen_write(const char *path, const char *fam_path, const char *const *names, size_t p, const float *data, size_t N,
+                    char *err, size_t err_len);
+
 /* `sepselect` / `orient-v-structs` hot loop: cusk_postprocessing/sepselect.py:262-329
  * (MergedCuskResults.find_maximal_and_min_pcorr_sepsets_incr) for a batch of outer pairs, one wavefront per pair.
  * All pointers are HOST memory.
