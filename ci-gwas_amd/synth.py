@@ -755,3 +755,341 @@ def deep_removal_case(levels=range(5, 15), seed: int = 0, N: int = 20000, extras
     np.fill_diagonal(Cm, 1.0)
     Cm = np.ascontiguousarray(Cm, np.float32)
     return (Cm, info) if return_info else Cm
+
+
+# ---------------------------------------------------------------- level-1 tests placed at the decision boundary
+# (name, N, alpha) of level1_band_thresholds(); the two sizes around kThMinFilter are derived, not written down
+LEVEL1_BAND_GRID = (0.05, 0.3, 0.5, 0.9, 0.999)
+LEVEL1_BAND_ULPS = (-4096, -256, -16, -2, -1, 0, 1, 2, 16, 256, 4096)
+LEVEL1_BAND_BETAS = (-2.0, -1.0, -0.5, 0.5, 1.0, 2.0)
+LEVEL1_BAND_SETS = 40
+# planted triples that need no flip: name -> (a = C[X,S], b = C[Y,S], c = C[X,Y], private leaf on X in the hub layout).
+# "1+" is the float behind 1 (a correlation that rounding pushed past 1: 1 - v v < 0); "ab" / "cb" is the float product
+# of the two other entries, which makes h01 exactly 0: the squared form then sees lhs = 0 > t2 (h00 hc) (1 + beta) with
+# h00 < 0 ("certainly dependent") where the exact form gets rho = 0 and removes the edge.
+LEVEL1_BAND_DEGENERATE = {
+    "a=+1": (1.0, 0.5, 0.45, False), "a=-1": (-1.0, 0.5, 0.45, False),
+    "a=b=+1": (1.0, 1.0, 0.5, False), "a=b=-1": (-1.0, -1.0, 0.5, False),
+    "hc<0": (0.6, 0.5, "1+", False),
+    "nan:a": (np.nan, 0.5, 0.45, False), "nan:b": (0.6, np.nan, 0.45, False), "nan:c": (0.6, 0.5, np.nan, False),
+    "c=+1": (0.6, 0.5, 1.0, False), "c=-1": (0.6, 0.5, -1.0, False),
+    "h00<0:a": ("1+", 0.5, "ab", False), "h00<0:a,leaf": ("1+", 0.5, "ab", True),
+    "h00<0:c": ("cb", 0.5, "1+", False), "h00<0:c,leaf": ("cb", 0.5, "1+", True),
+}
+
+
+def _csrc_constant(header: str, name: str) -> float:
+    """a `constexpr float name = <expression of float literals>;` of csrc/<header>"""
+    import os
+    import re
+
+    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", header)).read()
+    expr = re.search(r"constexpr\s+float\s+" + name + r"\s*=\s*([^;]+);", src).group(1)
+    return float(eval(re.sub(r"(?<=[0-9.])f\b", "", expr), {"__builtins__": {}}, {}))
+
+
+def _f32_ord(x) -> int:
+    """float32 -> integer whose order is the order of the floats (adjacent floats differ by 1)"""
+    i = int(np.float32(x).view(np.int32))
+    return i if i >= 0 else -(i & 0x7FFFFFFF)
+
+
+def _f32_from_ord(k: int) -> np.float32:
+    return np.int32(k).view(np.float32) if k >= 0 else np.float32(-(np.int32(-k).view(np.float32)))
+
+
+def level1_beta(t2) -> float:
+    """level1_beta of csrc/level1.hip for t2 = (float) tanh(th)^2, capped at kBeta of ci_fast.h.  It only places
+    inputs here."""
+    t = np.sqrt(max(float(np.float32(t2)), 1e-30))
+    return float(np.float32(min(_csrc_constant("ci_fast.h", "kBeta"), 16.0 * (2.0 * (2.4e-7 + 5.6e-8 / t) + 3.0e-7))))
+
+
+def level1_band_thresholds(alpha: float = 1e-4) -> dict:
+    """name -> (N, alpha) of the level-1 band cases.  `above_min` / `below_min`: the largest N whose Th[1] is still
+    >= kThMinFilter (the filter runs) and the next one (everything on the exact form), found on oracle.threshold_array."""
+    from oracle import oracle as O
+
+    th_min = np.float32(_csrc_constant("sweep_common.h", "kThMinFilter"))
+    lo, hi = 1000, 1 << 30  # Th[1] >= th_min at lo, < th_min at hi
+    assert O.threshold_array(lo, alpha)[1] >= th_min > O.threshold_array(hi, alpha)[1]
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if O.threshold_array(mid, alpha)[1] >= th_min:
+            lo = mid
+        else:
+            hi = mid
+    return {"n60": (60, 1e-2), "headline": (16384, alpha), "biobank": (500000, alpha), "above_min": (lo, alpha),
+            "below_min": (hi, alpha)}
+
+
+def _het_lth(th, sizes):
+    """ess_threshold_exact<1>: float sum of the int-truncated sizes (NaN -> 0) in the order (N[Y,X] + N[S,X]) + N[S,Y],
+    float division by 3, double square root and division, rounded to float"""
+    s = np.float32(0.0)
+    for v in sizes:
+        s = np.float32(s + np.float32(0.0 if np.isnan(v) else int(v)))
+    me = np.float32(s / np.float32(3.0))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.float32(np.float64(np.float32(th)) / np.sqrt(np.float64(me) - 4.0))
+
+
+def _het_size_classes(th, N0):
+    """[(name, (N[X,Y], N[X,S], N[Y,S]))]: sums of three sizes on both sides of kHetUMin, kHetUMax (u = th^2 / (me - 4))
+    and kHetDMin (me - 4), two adjacent sums on each side, in the float32 steps of the row kernel; N0 everywhere; one
+    class each with a NaN, a zero and a negative size"""
+    F = np.float32
+    th2 = F(np.float64(F(th)) ** 2)
+    umin, umax, dmin = (F(_csrc_constant("level1.hip", k)) for k in ("kHetUMin", "kHetUMax", "kHetDMin"))
+
+    def dm_u(s):
+        dm = F(F(F(s) * F(0.33333334)) - F(4.0))
+        return dm, F(th2 * F(F(1.0) / dm))
+
+    def first(pred, guess):
+        """smallest integer sum at which pred holds (pred is monotone around guess)"""
+        s = int(guess) - 64
+        assert not pred(s)
+        while not pred(s):
+            s += 1
+        return s
+
+    s_umin = first(lambda s: not dm_u(s)[1] >= umin, 3.0 * (float(th2) / float(umin) + 4.0))
+    s_umax = first(lambda s: dm_u(s)[1] <= umax, 3.0 * (float(th2) / float(umax) + 4.0))
+    s_dmin = first(lambda s: dm_u(s)[0] >= dmin, 3.0 * (float(dmin) + 4.0))
+    out = []
+    for name, s0 in (("umin", s_umin), ("umax", s_umax), ("dmin", s_dmin)):
+        for j in (-2, -1, 0, 1):
+            s = s0 + j
+            n1 = s // 3
+            n2 = (s - n1) // 2
+            out.append((f"{name}{j:+d}", (float(n1), float(n2), float(s - n1 - n2))))
+    out.append(("N0", (float(N0),) * 3))
+    out += [("nan", (np.nan, float(N0), float(N0))), ("zero", (float(N0), 0.0, float(N0))), ("negative", (float(N0), float(N0), -5.0))]
+    return out
+
+
+def level1_band_case(layout: str, N: int, alpha: float, mode: str = "skeleton", seed: int = 0):
+    """Symmetric float32 matrix (not positive definite: engine and oracle take any) of triples (X, Y, S) whose level-1 test
+    (X; Y | S) sits at the decision boundary, and what was placed where.
+
+    A parameter set is (a = C[X,S], b = C[Y,S], sign of rho): |a|, |b| from LEVEL1_BAND_GRID with a != b, every sign
+    pattern in turn, topped up with seeded random draws to LEVEL1_BAND_SETS sets.  A set is used only where the premises
+    can hold at the case's threshold t = tanh(Th[1]): |a|, |b|, |c| clear of the level-0 cut, the other tests of the triple
+    ((X; S | Y), (Y; S | X)) and, with a shared S, the tests of S given another triple's variable (rho = v / sqrt(1 - w^2))
+    at least 5 % off t^2 and 1 / t^2 in rho^2 (a |rho| > 1 of this indefinite matrix reads as 1 / |rho|).  The flip point c
+    of C[X,Y] is found by bisection over float32 bit patterns on the ORACLE's verdict for the 3 x 3 matrix (`mode`:
+    oracle.skeleton, oracle.hetcor_skeleton at one size, or at the triple's own three sizes for "het"): the edge X - Y
+    is removed at the float next to c on the side of a b and kept at c (for rho > 0 the smallest float at which it is kept,
+    for rho < 0 the largest).  Every set is instantiated, as triples of their own, at c + j ulp (LEVEL1_BAND_ULPS) and at
+    the values that move rho^2 by LEVEL1_BAND_BETAS x beta relative to c, beta = level1_beta at the set's threshold.
+    LEVEL1_BAND_DEGENERATE lists the planted triples that need no flip.
+
+    layout "cliques": disjoint 3-cliques on the diagonal (roles permuted over the three indices), everything else 0.
+    layout "hub": one S for all triples (degree 2 per triple plus fillers: more than two staging rounds of 512), a few
+    fillers before S, then the triples in seeded order with X / Y in either order, fillers (adjacent to S only, |f| in
+    [0.4, 0.7]) strewn between, and for every third triple a private leaf (adjacent to the first of X / Y only, +-0.5)
+    between the two, so that the triple's second variable is the SECOND position of a lane's pair in the row kernel.
+    n is not a multiple of 4.
+
+    mode "het": per-pair sample sizes.  The sets are dealt over _het_size_classes (two per class, the rest at N0); the
+    returned size matrix is bitwise symmetric with N0 outside the triples.
+
+    Returns (Cm, info) or, for "het", (Cm, Nm, info).  info: "Th" (skeleton) / "th", "N", "alpha", "t", "beta", "sets"
+    (a, b, s, c, sizes, cls, t, beta), "entries" (set or None, label, degenerate or None, X, Y, S, a, b, c, sizes, leaf),
+    "hub", "fillers", "leaves"."""
+    from oracle import oracle as O
+
+    assert layout in ("cliques", "hub") and mode in ("skeleton", "hetcor", "het")
+    F = np.float32
+    rng = np.random.default_rng(BASE_SEED + 977 * seed + (0 if mode != "het" else 1))
+    Th = O.threshold_array(N, alpha)
+    th = O.hetcor_threshold(alpha)
+    ones3, ti3 = np.ones((3, 3), np.int32), np.zeros(3, np.int32)
+
+    def kept(a, b, c, sizes):
+        C3 = np.array([[1, c, a], [c, 1, b], [a, b, 1]], F)
+        if mode == "skeleton":
+            return O.skeleton(C3, Th, 1).G[0, 1] == 1
+        nxy, nxs, nys = sizes
+        N3 = np.array([[np.nan, nxy, nxs], [nxy, np.nan, nys], [nxs, nys, np.nan]], F)
+        return O.hetcor_skeleton(C3, ones3, N3, th, 1, ti3).G[0, 1] == 1
+
+    def cuts(sizes):
+        """(t of the level-1 tests of the triple, level-0 cuts of X-Y, X-S, Y-S) in float64"""
+        if mode == "skeleton":
+            return float(np.tanh(np.float64(Th[1]))), (float(np.tanh(np.float64(Th[0]))),) * 3
+        with np.errstate(invalid="ignore", divide="ignore"):
+            t0 = np.tanh(np.float64(F(th)) / np.sqrt(np.array(sizes, np.float64) - 3.0))
+        return float(np.tanh(np.float64(_het_lth(th, sizes)))), tuple(0.0 if np.isnan(v) else float(v) for v in t0)
+
+    M = 0.05
+
+    def feasible(a, b, s, sizes):
+        t, (t0xy, t0xs, t0ys) = cuts(sizes)
+        a, b = float(F(a)), float(F(b))
+        vmax = 1.0 / np.sqrt(1.0 + t * t * (1.0 + M))
+        if mode == "het":  # a test of S given another triple's variable mixes the sizes of two classes: t up to 0.052
+            vmax = min(vmax, 0.95)
+        if not (t0xs * 1.02 <= abs(a) <= vmax and t0ys * 1.02 <= abs(b) <= vmax):
+            return False
+        c = a * b + s * t * np.sqrt((1 - a * a) * (1 - b * b))
+        if not (max(t0xy, t * 0.9) * 1.02 <= abs(c) <= 0.98):
+            return False
+        for v, w in ((a, b), (b, a)):  # (X; S | Y) and (Y; S | X)
+            r2 = (v - c * w) ** 2 / ((1 - c * c) * (1 - w * w))
+            if not (t * t * (1 + M) <= r2 <= 1.0 / (t * t * (1 + M))):
+                return False
+        return True
+
+    classes = _het_size_classes(th, N) if mode == "het" else [("N", (float(N),) * 3)]
+    combos = [(sa, sb, s) for sa in (1, -1) for sb in (1, -1) for s in (1, -1)]
+    cand = []
+    for i, (va, vb) in enumerate((va, vb) for va in LEVEL1_BAND_GRID for vb in LEVEL1_BAND_GRID if va != vb):
+        for j in range(8):
+            sa, sb, s = combos[(3 * i + j) % 8]
+            cand.append((sa * va, sb * vb, s))
+    cand = [cand[k] for i in range(8) for k in range(i, len(cand), 8)]  # every magnitude pair before its next sign pattern
+    # how many sets each class gets
+    if mode == "het":
+        quota = [2 if name != "N0" else 0 for name, _ in classes]
+        quota[[name for name, _ in classes].index("N0")] = LEVEL1_BAND_SETS - sum(quota)
+    else:
+        quota = [LEVEL1_BAND_SETS]
+    sets, used = [], set()
+    for ci, ((cname, sizes), q) in enumerate(zip(classes, quota)):
+        got = 0
+        grid_share = q if mode == "het" else (3 * q) // 4  # the rest are random draws
+        for k in range(len(cand)):
+            kk = (k + 7 * ci) % len(cand)
+            if got >= grid_share:
+                break
+            if kk in used or not feasible(*cand[kk], sizes):
+                continue
+            used.add(kk)
+            sets.append(dict(a=F(cand[kk][0]), b=F(cand[kk][1]), s=cand[kk][2], sizes=sizes, cls=cname))
+            got += 1
+        t, t0 = cuts(sizes)
+        tries = 0
+        while got < q:
+            tries += 1
+            if tries > 20000:
+                raise ValueError(f"level1_band_case: no feasible parameter set for size class {cname}")
+            lo = max(1.1 * max(t0[1], t0[2], t), 0.02)
+            a, b = (rng.uniform(min(lo, 0.95), 0.95, 2) * rng.choice([-1.0, 1.0], 2)).tolist()
+            s = int(rng.choice([-1, 1]))
+            if F(a) != F(b) and feasible(a, b, s, sizes):
+                sets.append(dict(a=F(a), b=F(b), s=s, sizes=sizes, cls=cname))
+                got += 1
+
+    entries = []
+    for si, p in enumerate(sets):
+        a, b, s, sizes = p["a"], p["b"], p["s"], p["sizes"]
+        t, _ = cuts(sizes)
+        beta = level1_beta(F(t * t))
+        ab = float(a) * float(b)
+        D = np.sqrt((1 - float(a) ** 2) * (1 - float(b) ** 2))
+        # (a far end just past the flip: farther out C[X,Y] can fall below the level-0 cut when a b and rho differ in sign)
+        lo, hi = s * _f32_ord(F(ab)), s * _f32_ord(F(ab + s * 1.005 * t * D))
+        f = lambda k: kept(a, b, _f32_from_ord(s * k), sizes)  # noqa: E731
+        if not (lo < hi and not f(lo) and f(hi)):
+            raise ValueError(f"level1_band_case: no flip for set {si} {p}")
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            if f(mid):
+                hi = mid
+            else:
+                lo = mid
+        c = _f32_from_ord(s * hi)
+        p.update(c=c, t=t, beta=beta)
+        ladder = [(f"{j:+d}ulp", _f32_from_ord(_f32_ord(c) + j)) for j in LEVEL1_BAND_ULPS]
+        ladder += [(f"{r:+g}beta", F(ab + (float(c) - ab) * np.sqrt(1.0 + r * beta))) for r in LEVEL1_BAND_BETAS]
+        for label, cv in ladder:
+            entries.append(dict(set=si, label=label, degenerate=None, a=a, b=b, c=F(cv), sizes=sizes, want_leaf=(len(entries) % 3 == 0)))
+    onep = np.nextafter(F(1.0), F(2.0))
+    for name, (a, b, c, leaf) in LEVEL1_BAND_DEGENERATE.items():
+        b = F(b)
+        a = onep if isinstance(a, str) and a == "1+" else a
+        c = onep if isinstance(c, str) and c == "1+" else c
+        if isinstance(c, str):  # "ab"
+            c = F(F(a) * b)
+        if isinstance(a, str):  # "cb"
+            a = F(F(c) * b)
+        entries.append(dict(set=None, label=name, degenerate=name, a=F(a), b=b, c=F(c), sizes=(float(N),) * 3, want_leaf=leaf))
+
+    E = len(entries)
+    fillers, leaves, hub = [], [], None
+    if layout == "cliques":
+        n = 3 * E
+        n += 1 if n % 4 == 0 else 0
+        perms = [(0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)]
+        for k, e in enumerate(entries):
+            pm = perms[k % 6]
+            e.update(X=3 * k + pm[0], Y=3 * k + pm[1], S=3 * k + pm[2], leaf=None)
+        leaf_val = {}
+    else:
+        seq = [("F", -1)] * 6 + [("S", -1)]
+        for k in rng.permutation(E):
+            e = entries[k]
+            if (e["degenerate"] or "").startswith("h00<0:a"):
+                continue  # |C[X,S]| > 1 would separate everything from a shared S: these get an S of their own, below
+            if rng.random() < 0.22:
+                seq.append(("F", -1))
+            first, second = ("X", "Y") if (rng.random() < 0.5 or e["degenerate"]) else ("Y", "X")
+            seq.append((first, k))
+            if e["want_leaf"]:
+                seq.append(("L", k))
+            if rng.random() < 0.10:
+                seq.append(("F", -1))
+            seq.append((second, k))
+        for k, e in enumerate(entries):
+            if (e["degenerate"] or "").startswith("h00<0:a"):
+                seq += [("P", k), ("X", k)] + ([("L", k)] if e["want_leaf"] else []) + [("Y", k)]
+        while len(seq) % 4 == 0 or len(seq) % 4 == 1:  # n = 2 or 3 mod 4
+            seq.append(("F", -1))
+        n = len(seq)
+        for e in entries:
+            e["leaf"] = None
+        leaf_val = {}
+        for idx, (kind, k) in enumerate(seq):
+            if kind == "S":
+                hub = idx
+            elif kind == "F":
+                fillers.append(idx)
+            elif kind == "P":
+                entries[k]["S"] = idx
+            elif kind == "L":
+                entries[k]["leaf"] = idx
+                leaves.append(idx)
+                leaf_val[idx] = F(0.5 * rng.choice([-1.0, 1.0]))
+            else:
+                entries[k][kind] = idx
+        for e in entries:
+            e.setdefault("S", hub)
+            e["leaf_of"] = None if e["leaf"] is None else ("X" if e["X"] < e["Y"] else "Y")
+    Cm = np.zeros((n, n), F)
+    np.fill_diagonal(Cm, 1.0)
+    Nm = np.full((n, n), F(N), F) if mode == "het" else None
+
+    def put(M_, i, j, v):
+        M_[i, j] = M_[j, i] = v
+
+    for e in entries:
+        X, Y, S = e["X"], e["Y"], e["S"]
+        put(Cm, X, S, e["a"])
+        put(Cm, Y, S, e["b"])
+        put(Cm, X, Y, e["c"])
+        if Nm is not None:
+            put(Nm, X, Y, F(e["sizes"][0]))
+            put(Nm, X, S, F(e["sizes"][1]))
+            put(Nm, Y, S, F(e["sizes"][2]))
+        if e.get("leaf") is not None:
+            put(Cm, e["leaf"], e[e["leaf_of"]], leaf_val[e["leaf"]])
+        e.pop("want_leaf")
+    for f_ in fillers:
+        put(Cm, f_, hub, F(rng.uniform(0.4, 0.7) * rng.choice([-1.0, 1.0])))
+    t_all, _ = cuts((float(N),) * 3)
+    info = dict(layout=layout, mode=mode, N=N, alpha=alpha, Th=Th, th=th, t=t_all, beta=level1_beta(F(t_all * t_all)), sets=sets,
+                entries=entries, hub=hub, fillers=fillers, leaves=leaves, size_classes=classes)
+    Cm = np.ascontiguousarray(Cm)
+    return (Cm, np.ascontiguousarray(Nm), info) if mode == "het" else (Cm, info)
