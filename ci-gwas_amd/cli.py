@@ -8,7 +8,7 @@ the native `mps` program with literal 'NULL' for absent paths, `subprocess.run(c
 `cuskss-het` and `cuskss-merged` (README.md:65,75 of the reference names them, its CLI does
 not define them) are aliases of `cuskss` that insist on the flags that select that mode.
 The workflow is prune-bed -> prep-bed -> prep-phen -> block -> cusk -> merge-block-outputs -> cuskss-merged -> sepselect ->
-check-ivs.
+check-ivs -> mvivw.
 `prune-bed` is not in the reference: its README asks for a fileset that is LD pruned ("or at least does not have markers
 with a correlation of 1") and has no marker without recorded variation, and leaves both to the user.  Here they are
 decided on the device, on the banded Kendall-npn correlation that `block` and the skeleton use (`mps prune`): markers in
@@ -32,8 +32,11 @@ decide at the per-pair sample sizes a heterogeneous `cuskss-merged` run left in 
 package's mirror of the reference's merge module (ci-gwas_amd/merge.py), pinned by files the reference's own code
 wrote (tests/golden/merge).  `iv-candidates` and `check-ivs` write the instrument tables of the reference's
 cusk_postprocessing/check_mr_assumptions.py (`get_iv_candidates`, `check_ivs`; its CLI reaches them through `mvivw`) from a
-merged skeleton, the tests of `check-ivs` on the device (ci-gwas_amd/ivcheck.py).  The rest of the downstream (the R
-estimators of srfci and mvivw) is the reference's own code and consumes the files written here unchanged.
+merged skeleton, the tests of `check-ivs` on the device (ci-gwas_amd/ivcheck.py).  `mvivw` (ci-gwas.py:272-301, :479-503) writes the
+candidate table and then the multivariable IVW estimates of every outcome, computed on the device (ci-gwas_amd/mvivw.py):
+the plain IVW estimator with multiplicative random effects, NOT the reference's `mr_mvivw(..., robust = TRUE)`, which needs
+R and robustbase::lmrob and can be neither run nor restated here.  The rest of the downstream (the R code of srfci) is the
+reference's own code and consumes the files written here unchanged.
 """
 from __future__ import annotations
 
@@ -264,6 +267,32 @@ def _add_ivcheck(sub):
     p.set_defaults(func=run_check_ivs)
 
 
+def _add_mvivw(sub):
+    """ci-gwas.py:272-301, with the selections of both of the reference's R scripts and the choices the R back-end fixes"""
+    p = sub.add_parser("mvivw", help="Multivariable inverse-variance weighted Mendelian randomisation between the traits, "
+                                     "using cusk-identified markers as instrumental variables: the plain IVW estimator with "
+                                     "multiplicative random effects, not the reference's robust one (requires GPU)")
+    p.add_argument("cusk_output_stem", metavar="cusk-output-stem", type=str, help="output stem of cusk or cuskss result files")
+    p.add_argument("num_samples", metavar="num-samples", type=TypeCheck(int, "num-samples", 1, None),
+                   help="number of samples used for computing correlations")
+    which = p.add_mutually_exclusive_group()
+    which.add_argument("-s", action="store_true", help="use cusk inferred trait-trait skeleton to select exposures")
+    which.add_argument("--orientation-prior", metavar="orientation-prior", type=str, default=None,
+                       help="matrix of (0, 1) (32 bit integers, binary) of dims (n_trait, n_trait) indicating directions to be "
+                            "forced. ")
+    which.add_argument("--ivs", metavar="FILE", type=str, default=None,
+                       help="table Exposure,Outcome,IV (as check-ivs writes it) that names the exposures and instruments of "
+                            "every outcome")
+    p.add_argument("--het", action="store_true",
+                   help="weights from the per-pair sample sizes of <cusk-output-stem>_ssz.mtx (written by cuskss-merged --het) "
+                        "instead of num-samples, which is then not used")
+    p.add_argument("--model", choices=("default", "random", "fixed"), default="default",
+                   help="standard errors: random = multiplicative random effects, fixed, default = random with four or more "
+                        "instruments")
+    p.add_argument("--out", type=str, default=None, help="output file (default <cusk-output-stem>_mvivw_results.tsv)")
+    p.set_defaults(func=run_mvivw)
+
+
 def build_parser() -> argparse.ArgumentParser:
     parser = _Parser(prog="ci-gwas", description="cusk / cuskss steps of CI-GWAS on AMD Instinct MI355X")
     sub = parser.add_subparsers(required=True, title="subcommands")
@@ -279,6 +308,7 @@ def build_parser() -> argparse.ArgumentParser:
     _add_merge(sub)
     _add_sepselect(sub)
     _add_ivcheck(sub)
+    _add_mvivw(sub)
     return parser
 
 
@@ -543,6 +573,29 @@ def run_check_ivs(args):
                      check_reverse_causality=args.check_reverse_causality, het=args.het, engine=Engine(0), data=data)
     write_csv(args.out or f"{args.cusk_output_stem}_ivs.csv", rows)
     print(f"check-ivs: {len(rows)} instrument rows.")
+
+
+def _mvivw_engine():
+    from .skeleton import Engine
+
+    return Engine(0)
+
+
+def run_mvivw(args):
+    """ci-gwas.py:479-503: the candidate table first, then the estimates (here on the device instead of in R)"""
+    from . import mvivw
+    from .ivcheck import iv_candidates, load, write_csv
+
+    stem = args.cusk_output_stem
+    data = load(stem, het=args.het)  # unreadable inputs are reported before an engine exists; read once
+    write_csv(f"{stem}_iv_candidates.csv", iv_candidates(stem, data=data))
+    mode = "skeleton" if args.s else "prior" if args.orientation_prior else "ivs" if args.ivs else "all"
+    res = mvivw.run(stem, args.num_samples, mode=mode, prior_path=args.orientation_prior, ivs_path=args.ivs, het=args.het,
+                    model=mvivw.MODELS[args.model], engine=_mvivw_engine(), data=data)
+    out = args.out or f"{stem}_mvivw_results.tsv"
+    mvivw.write_results(out, res)
+    mvivw.write_outcomes(f"{out[:-len('_results.tsv')]}_outcomes.tsv" if out.endswith("_results.tsv") else f"{out}.outcomes.tsv", res)
+    print(f"mvivw: {int((res['status'] == 0).sum())} of {res['p']} outcomes estimated.")
 
 
 def main(argv=None):

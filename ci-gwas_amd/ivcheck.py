@@ -73,9 +73,10 @@ def _rows(per_pair, p: int):
     return rows
 
 
-def iv_candidates(stem: str):
-    """get_iv_candidates: every candidate of the exposure, for every (exposure, outcome) pair"""
-    adj, _, p, _ = load(stem)
+def iv_candidates(stem: str, data=None):
+    """get_iv_candidates: every candidate of the exposure, for every (exposure, outcome) pair.  `data`: what `load(stem)`
+    returned, to spare reading the files again."""
+    adj, _, p, _ = load(stem) if data is None else data
     cands = _candidates(adj, p)
     return _rows({(e, o): cands[e].tolist() for e in range(p) for o in range(p) if e != o}, p)
 

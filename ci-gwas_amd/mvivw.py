@@ -1,0 +1,277 @@
+"""`ci-gwas mvivw`: multivariable inverse-variance-weighted causal effects between the traits of a merged skeleton.
+
+Counterpart of the reference's mvivw/cig_mvivw.R and cig_mvivw_filtered.R, written from their semantics: for every outcome
+trait one weighted regression through the origin of the outcome's marker correlations on those of its exposures, over the
+outcome's instruments.
+
+NOT the reference's estimator.  The reference calls `mr_mvivw(..., robust = TRUE)` of the R package MendelianRandomization,
+which uses `robustbase::lmrob`: an MM-estimator with random subsampling.  Neither R nor that package is on our machines and
+its program text is not in the reference tree; it can be neither run nor restated, so nothing here claims to equal it.
+This module computes the plain IVW estimator with multiplicative random effects: weighted least squares through the
+origin with a standard-error inflation.  To our knowledge that is what the package computes with `robust = FALSE`; nobody
+has checked this against R.  The rule is stated in include/cusk_hip.h above `cusk_mvivw` (csrc/mvivw.hip on the device,
+`HostEngine` below in float64 numpy with the same chunked sums, used when no engine is given).
+
+Inputs as for `check-ivs` (`ivcheck.load`): `<stem>_sam.mtx`, `<stem>_scm.mtx`, `<stem>.mdim`; traits are variables
+0 .. p-1, marker row r is variable p + r, beta = corr[p:, :p], weight = 1 / byse^2 with byse = (1 - beta^2) / sqrt(N - 2)
+(the reference's `SE`).  With `het` N is the size of marker and outcome in `<stem>_ssz.mtx`; a size <= 2 makes the weight
+non-positive or non-finite and gives the outcome status 3.  Adjacency means `!= 0`, as in ivcheck.py.
+
+Selections of the instruments I and exposures E of outcome o:
+  all       E = every trait != o; I = markers not adjacent to o (the reference's default)
+  skeleton  E = traits adjacent to o; I = markers adjacent neither to o nor to any trait that is not adjacent to o
+  prior     E = traits t != o with prior[o, t] != 1 (p x p int32, row-major); I = markers not adjacent to o
+  ivs       E and I = the distinct exposures and IVs a table `Exposure,Outcome,IV` (as `check-ivs` writes it: 1-based, IV
+            counted from the first marker) lists for o
+Deliberate deviations from the reference's scripts:
+  * skeleton: the reference's `B[-rm_rows, ]` with an empty `rm_rows` selects ZERO rows in R; here an empty removal
+    removes nothing.
+  * prior: the reference also drops the marker rows whose row numbers happen to equal the removed trait numbers (it mixes
+    the two index spaces); we do not.
+  * `num_snps` is the outcome's own m; the reference's column carries one recycled value (the `num_snp` / `num_snps` slip
+    of its script).
+"""
+from __future__ import annotations
+
+import sys
+
+import numpy as np
+
+from . import ivcheck
+
+CHUNK = 256          # CUSK_MVIVW_CHUNK
+MAX_EXPOSURES = 127  # CUSK_MVIVW_MAX_EXPOSURES
+PIVOT_MIN = 1e-8     # CUSK_PHEN_PIVOT_MIN
+MODELS = {"default": 0, "random": 1, "fixed": 2}
+
+
+def weights(beta, n):
+    """1 / byse^2, byse = (1 - beta^2) / sqrt(n - 2); n a number or an array in the layout of beta"""
+    with np.errstate(all="ignore"):
+        byse = (1.0 - beta * beta) / np.sqrt(np.asarray(n, np.float64) - 2.0)
+        return np.array(np.broadcast_to(1.0 / (byse * byse), beta.shape), dtype=np.float64, order="C")
+
+
+def read_prior(path: str, p: int):
+    prior = np.fromfile(path, dtype=np.int32)
+    if prior.size != p * p:
+        raise ValueError(f"{path}: expected {p} x {p} 32-bit integers, found {prior.size}")
+    return prior.reshape(p, p)
+
+
+def read_ivs(path: str):
+    """the rows (Exposure, Outcome, IV) of a table written by ivcheck.write_csv"""
+    with open(path) as f:
+        header = f.readline().strip()
+        if header != "Exposure,Outcome,IV":
+            raise ValueError(f"{path}: the header is not Exposure,Outcome,IV")
+        rows = [tuple(int(v) for v in line.split(",")) for line in f if line.strip()]
+    if any(len(r) != 3 for r in rows):
+        raise ValueError(f"{path}: a row does not have three fields")
+    return rows
+
+
+def select(adj, p: int, mode: str = "all", prior=None, iv_rows=None):
+    """[(I, E)] per outcome: ascending int arrays of marker rows and exposure traits"""
+    adj = np.asarray(adj)
+    M = adj.shape[0] - p
+    mxp = adj[:p, p:].T != 0  # M x p
+    pxp = adj[:p, :p] != 0
+    traits = np.arange(p)
+    out = []
+    if mode == "ivs":
+        rows = np.asarray(iv_rows, np.int64).reshape(-1, 3)
+        if rows.size and (rows[:, :2].min() < 1 or rows[:, :2].max() > p or rows[:, 2].min() < 1 or rows[:, 2].max() > M):
+            raise ValueError("mvivw: the instrument table names a trait or a marker the skeleton does not have")
+        if np.any(rows[:, 0] == rows[:, 1]):
+            raise ValueError("mvivw: the instrument table lists a trait as its own exposure")
+        for o in range(p):
+            mine = rows[rows[:, 1] == o + 1]
+            out.append((np.unique(mine[:, 2]) - 1, np.unique(mine[:, 0]) - 1))
+        return out
+    for o in range(p):
+        keep = ~mxp[:, o]
+        if mode == "all":
+            E = traits[traits != o]
+        elif mode == "skeleton":
+            near = pxp[:, o].copy()
+            near[o] = False
+            E = traits[near]
+            keep &= ~mxp[:, ~near].any(axis=1)  # ~near holds o itself
+        elif mode == "prior":
+            E = traits[(np.asarray(prior)[o, :] != 1) & (traits != o)]
+        else:
+            raise ValueError(f"mvivw: unknown selection {mode!r}")
+        out.append((np.flatnonzero(keep), E))
+    return out
+
+
+def pack(selection):
+    """the list arguments of the engine call"""
+    nout = len(selection)
+    iv_off, ex_off = np.zeros(nout + 1, np.int64), np.zeros(nout + 1, np.int32)
+    iv_off[1:] = np.cumsum([len(I) for I, _ in selection])
+    ex_off[1:] = np.cumsum([len(E) for _, E in selection])
+    iv = np.concatenate([np.asarray(I, np.int32) for I, _ in selection]) if nout else np.zeros(0, np.int32)
+    ex = np.concatenate([np.asarray(E, np.int32) for _, E in selection]) if nout else np.zeros(0, np.int32)
+    return iv_off, iv.astype(np.int32), ex_off, ex.astype(np.int32)
+
+
+def check_arguments(M, p, outcome, iv_off, iv, ex_off, ex, model):
+    """the argument errors of cusk_mvivw (csrc/host/mvivw_plan.h), as a ValueError"""
+    if model not in (0, 1, 2):
+        raise ValueError(f"mvivw: model {model} is not 0 (default), 1 (random) or 2 (fixed)")
+    if np.any(np.diff(iv_off) < 0) or np.any(np.diff(ex_off) < 0) or (len(iv_off) and (iv_off[0] < 0 or ex_off[0] < 0)):
+        raise ValueError("mvivw: offsets are not monotone")
+    for a, o in enumerate(outcome):
+        I, E = iv[iv_off[a]:iv_off[a + 1]], ex[ex_off[a]:ex_off[a + 1]]
+        if not 0 <= o < p:
+            raise ValueError(f"mvivw: outcome {a}: {o} is not a trait index")
+        if len(E) > MAX_EXPOSURES:
+            raise ValueError(f"mvivw: outcome {a}: more than {MAX_EXPOSURES} exposures")
+        if len(I) and (I.min() < 0 or I.max() >= M or np.any(np.diff(I) <= 0)):
+            raise ValueError(f"mvivw: outcome {a}: the instrument list is not strictly ascending inside [0, M)")
+        if len(E) and (E.min() < 0 or E.max() >= p or np.any(np.diff(E) <= 0) or np.any(E == o)):
+            raise ValueError(f"mvivw: outcome {a}: the exposure list is not strictly ascending inside [0, p) without the outcome")
+
+
+def solve_one(X, y, w, model: int):
+    """One problem by the rule of include/cusk_hip.h -> (status, theta, se, (rss, sigma, smallest squared pivot))"""
+    from scipy.linalg import solve_triangular
+
+    m, k = X.shape
+    nan3 = (np.nan, np.nan, np.nan)
+    if k == 0 or m <= k:
+        return 1, None, None, nan3
+    if not (np.isfinite(X).all() and np.isfinite(y).all() and np.isfinite(w).all() and (w > 0).all()):
+        return 3, None, None, nan3
+    Z = np.concatenate([X, y[:, None]], axis=1)
+    S = np.zeros((k + 1, k + 1))
+    for c0 in range(0, m, CHUNK):  # chunk partials, added in chunk order
+        Zc = Z[c0:c0 + CHUNK]
+        S += (Zc * w[c0:c0 + CHUNK, None]).T @ Zc
+    G, b = S[:k, :k], S[k, :k]
+    dg = np.diag(G)
+    if not (dg > 0).all():
+        return 2, None, None, (np.nan, np.nan, 0.0)
+    d = np.sqrt(dg)
+    L = np.tril(G / np.outer(d, d))
+    np.fill_diagonal(L, 1.0)
+    minpiv = np.inf
+    for j in range(k):  # right-looking Cholesky with the pivot test
+        piv = L[j, j]
+        minpiv = min(minpiv, piv)
+        if not piv >= PIVOT_MIN:
+            return 2, None, None, (np.nan, np.nan, float(piv))
+        L[j, j] = np.sqrt(piv)
+        L[j + 1:, j] /= L[j, j]
+        L[j + 1:, j + 1:] -= np.tril(np.outer(L[j + 1:, j], L[j + 1:, j]))
+    Linv = solve_triangular(L, np.eye(k), lower=True)
+    theta = (Linv.T @ (Linv @ (b / d))) / d
+    v = (Linv * Linv).sum(axis=0) / (d * d)
+    r = y - X @ theta
+    t = w * (r * r)
+    rss = 0.0
+    for c0 in range(0, m, CHUNK):  # the second pass, same chunks
+        rss += float(t[c0:c0 + CHUNK].sum())
+    sigma = float(np.sqrt(rss / (m - k)))
+    random = model == 1 or (model == 0 and m >= 4)
+    se = np.sqrt(v) * (sigma if random and sigma > 1.0 else 1.0)
+    return 0, theta, se, (rss, sigma, float(minpiv))
+
+
+class HostEngine:
+    """`Engine.mvivw` in float64 numpy: what `mvivw(engine=None)` runs on, and the comparison form of the tests"""
+
+    def mvivw(self, beta, weight, outcome, iv_off, iv, ex_off, ex, model=0):
+        beta, weight = np.asarray(beta, np.float64), np.asarray(weight, np.float64)
+        M, p = beta.shape
+        outcome = np.asarray(outcome, np.int64).reshape(-1)
+        iv_off, ex_off = np.asarray(iv_off, np.int64).reshape(-1), np.asarray(ex_off, np.int64).reshape(-1)
+        iv, ex = np.asarray(iv, np.int64).reshape(-1), np.asarray(ex, np.int64).reshape(-1)
+        check_arguments(M, p, outcome, iv_off, iv, ex_off, ex, model)
+        nout = outcome.shape[0]
+        nex = int(ex_off.max()) if nout else 0
+        theta, se = np.full(max(nex, 1), np.nan), np.full(max(nex, 1), np.nan)
+        stats, status = np.full((nout, 3), np.nan), np.zeros(nout, np.int32)
+        for a, o in enumerate(outcome):
+            I, E = iv[iv_off[a]:iv_off[a + 1]], ex[ex_off[a]:ex_off[a + 1]]
+            st, th, s, stat = solve_one(beta[np.ix_(I, E)], beta[I, o], weight[I, o], model)
+            status[a], stats[a] = st, stat
+            if st == 0:
+                theta[ex_off[a]:ex_off[a + 1]] = th
+                se[ex_off[a]:ex_off[a + 1]] = s
+        return theta, se, stats, status, 0.0
+
+
+def run(stem: str, num_samples: int, mode: str = "all", prior_path: str | None = None, ivs_path: str | None = None,
+        het: bool = False, model: int = 0, engine=None, data=None):
+    """The estimates of every outcome of a merged skeleton.  `engine`: a device Engine (skeleton.Engine), or None for the
+    numpy form.  `data`: what `ivcheck.load(stem, het)` returned.  Returns a dict: p, selection [(I, E)], theta, se (lists
+    per outcome, None unless status 0), stats, status, sk_adj (p x p bool), kernel_ms."""
+    adj, corr, p, ssz = ivcheck.load(stem, het=het) if data is None else data
+    beta = np.ascontiguousarray(corr[p:, :p])
+    weight = weights(beta, ssz[p:, :p] if het else num_samples)
+    prior = read_prior(prior_path, p) if mode == "prior" else None
+    iv_rows = read_ivs(ivs_path) if mode == "ivs" else None
+    selection = select(adj, p, mode, prior=prior, iv_rows=iv_rows)
+    for o, (_, E) in enumerate(selection):
+        if len(E) > MAX_EXPOSURES:
+            raise ValueError(f"mvivw: outcome trait {o + 1} (1-based) has {len(E)} exposures; at most {MAX_EXPOSURES} are supported")
+    iv_off, iv, ex_off, ex = pack(selection)
+    eng = engine if engine is not None else HostEngine()
+    theta, se, stats, status, ms = eng.mvivw(beta, weight, np.arange(p, dtype=np.int32), iv_off, iv, ex_off, ex, model)
+    ok = [int(status[o]) == 0 for o in range(p)]
+    return {"p": p, "selection": selection, "status": np.asarray(status[:p]).copy(), "stats": np.asarray(stats[:p]).copy(),
+            "theta": [np.array(theta[ex_off[o]:ex_off[o + 1]]) if ok[o] else None for o in range(p)],
+            "se": [np.array(se[ex_off[o]:ex_off[o + 1]]) if ok[o] else None for o in range(p)],
+            "sk_adj": np.asarray(adj)[:p, :p] != 0, "kernel_ms": ms}
+
+
+def _g(v) -> str:
+    return "%.15g" % v
+
+
+def write_results(path: str, res) -> None:
+    """`<stem>_mvivw_results.tsv`: one row per ordered pair, outcome outer, exposure inner, both 1-based"""
+    from scipy.special import ndtr
+
+    p = res["p"]
+    with open(path, "w") as f:
+        f.write("source\tsink\teffect\tp\tsk_adj\tnum_snps\tse\n")
+        for o in range(p):
+            I, E = res["selection"][o]
+            st = int(res["status"][o])
+            pos = {int(t): j for j, t in enumerate(E)}
+            if st in (2, 3):
+                print(f"mvivw: outcome trait {o + 1} (1-based): status {st}, no estimates", file=sys.stderr)
+            for e in range(p):
+                if e == o:
+                    continue
+                if e not in pos or st == 1:
+                    eff, pv, se = "0", "1", "NA"  # the reference's fill
+                elif st != 0:
+                    eff, pv, se = "NA", "NA", "NA"
+                else:
+                    th, s = float(res["theta"][o][pos[e]]), float(res["se"][o][pos[e]])
+                    with np.errstate(all="ignore"):
+                        eff, pv, se = _g(th), _g(2.0 * ndtr(-abs(np.float64(th) / np.float64(s)))), _g(s)
+                adjacent = "TRUE" if res["sk_adj"][e, o] else "FALSE"
+                f.write(f"{e + 1}\t{o + 1}\t{eff}\t{pv}\t{adjacent}\t{len(I)}\t{se}\n")
+
+
+def write_outcomes(path: str, res) -> None:
+    """`<stem>_mvivw_outcomes.tsv`: per outcome the heterogeneity statistic q = rss and its upper chi-square tail"""
+    from scipy.stats import chi2
+
+    with open(path, "w") as f:
+        f.write("sink\tn_exposures\tnum_snps\tsigma\tq\tq_p\tstatus\n")
+        for o in range(res["p"]):
+            I, E = res["selection"][o]
+            st = int(res["status"][o])
+            if st == 0:
+                rss, sigma = float(res["stats"][o][0]), float(res["stats"][o][1])
+                cols = (_g(sigma), _g(rss), _g(float(chi2.sf(rss, len(I) - len(E)))))
+            else:
+                cols = ("NA", "NA", "NA")
+            f.write(f"{o + 1}\t{len(E)}\t{len(I)}\t" + "\t".join(cols) + f"\t{st}\n")

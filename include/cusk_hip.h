@@ -131,7 +131,9 @@ const char *cusk_last_error(const cusk_engine *e);
  * cross-check kernels instead of the matrix cores), "corr_mxp_f32" (default 0: SNP x trait sums on the bf16 matrix pipe with every
  * trait value split exactly into three bf16 pieces; 1: the f32 matrix instructions of rounds 1-2), "assume_symmetric" (default 0: level 0 verifies C == C^T bitwise;
  * 1: the caller guarantees it, e.g. a matrix written by cusk_corr_build), "queue_capacity" (recheck queue entries, default 4Mi), "chunk" (combination ranks per work item, default 2048), "timing" (HIP events for cusk_stats: 0 total_ms only; 1, the default, around every level's sweep: kernel_ms, and level_ms = end of the previous level's sweep to the end of this one's; 2 also level start / end: level_ms = plan to finaliser; 3 only the pair around the level-1 row kernel: main_kernel_ms[1] -- every event costs a few microseconds of device time), "chunk0" (conditioning sets per work item of the first degree class, default 512), "tmaj_min_level" (first level swept by unions T = S + Y, one inverse per l + 1 tests: default 6, 99 = never; single threshold and symmetric matrix only), "tmaj_validate_stride" (with "validate": the union-major sweep checks the unions whose per-lane count is a multiple of this power of two against double precision; default 1 = all), "hostprof" (1: host-side phase marks of every run on stderr), "max_staged_classes" (test hook: at most this many degree classes keep their sub-matrix in LDS; 0 sends every row through the kernels of the unstaged class), "chunk0_low" (work-item size of the first degree class at levels 2-4, default 256), "vec_threads" (workgroup size of the vectorised sweep for the first degree class: 64, 128 or 256; default 64), "lookahead" (levels the host enqueues ahead of the level counters it has seen, default 2; every kernel checks its level's gate on the device), "sync2" (default 1: the host reads level 2's gate record -- class counts, maximum degree -- before it enqueues that level's sweeps, so that degree classes that turn out empty are not launched at levels >= 2; 0: enqueue ahead on the level-1 degree bound), "item_capacity" (work items per degree class and level the buffers hold before the engine grows them and takes the level up again, default 1Mi), "het_filter" (default 0: cusk_run_skeleton_het / cusk_run_skeleton_batch_het run every level on the exact path; 1: their levels >= 2 go through the filter at the per-test threshold and the recheck queue like the other modes, "fast" = 0 still selects the exact path, and "validate" is accepted), "het_rows" (0 or 1, default 0: level 1 of cusk_run_skeleton_het / cusk_run_skeleton_batch_het runs on the exact sweep; 1: on the row-streaming level-1 kernel at per-pair sample sizes when "fast", "pair" and "rows" are non-zero and both C and N_dev are symmetric, N_dev bit for bit -- otherwise as with 0; same results; cusk_engine_level1_form tells which kernel ran), "sepselect_ws_bytes" (HBM work space of
- * cusk_sepselect_greedy for candidate lists too long for LDS, default 4 GiB; such pairs run in batches of what fits). */
+ * cusk_sepselect_greedy for candidate lists too long for LDS, default 4 GiB; such pairs run in batches of what fits), "mvivw_part_bytes" (HBM of cusk_mvivw's chunk partials alive at
+ * once, default 256 MiB; outcomes run in groups of what fits, an outcome that alone exceeds it as a group of its own; the
+ * results do not depend on it). */
 int cusk_engine_set_option(cusk_engine *e, const char *key, long long value);
 /* Host only, no device needed: the workgroup size level 1's row-streaming kernel runs with when a row of C takes
  * row_bytes of LDS (4 (n + 8) for a single n x n matrix), or 0 when it gathers the row through the caches instead.
@@ -666,6 +668,51 @@ int cusk_iv_check(cusk_engine *e, const double *trait_corr, long long n, int p, 
 int cusk_iv_check_het(cusk_engine *e, const double *trait_corr, long long n, int p, int nsets, const int *set_off,
                       const int *set, long long nitems, const int *item_x, const int *item_y, const int *item_set,
                       const int *trait_n, double q, double *z, int *flags, float *kernel_ms);
+
+/* `mvivw`: multivariable inverse-variance-weighted regression of every outcome trait of a merged skeleton on its exposures
+ * (the step of mvivw/cig_mvivw.R and cig_mvivw_filtered.R), many independent problems in one call.  All pointers are HOST
+ * memory.
+ * NOT the reference's estimator: the reference calls mr_mvivw(..., robust = TRUE) of the R package MendelianRandomization,
+ * which uses robustbase::lmrob, an MM-estimator with random subsampling.  Neither R nor that package is on our machines
+ * and its program text is not in the reference tree: it can be neither run nor restated, so nothing here claims to equal
+ * it.  What is computed is the plain IVW estimator with multiplicative random effects: weighted least squares through the
+ * origin with a standard-error inflation.  To our knowledge that is what the package computes with robust = FALSE; nobody
+ * has checked this against R.
+ *   beta        M x p doubles, row-major: corr[p + r, t] of marker row r (variable p + r) with trait t
+ *   weight      M x p doubles, layout of beta: the weight of marker row r in the regression of outcome t; from Python
+ *               1 / byse^2 with byse = (1 - beta^2) / sqrt(N - 2), the reference's SE
+ *   outcome     nout outcome traits o, each in [0, p)
+ *   iv_off/iv   nout + 1 offsets into iv; iv = the instrument rows I of an outcome, in [0, M), strictly ascending; m = |I|
+ *   ex_off/ex   nout + 1 offsets into ex; ex = the exposure traits E of an outcome, in [0, p), strictly ascending, without
+ *               o; k = |E| <= 127
+ *   model       0 default, 1 random, 2 fixed (below)
+ * The rule per outcome, IEEE double throughout.  X = beta[I, E], y = beta[I, o], w = weight[I, o].
+ *   1. G = X'WX and b = X'Wy, summed over chunks of CUSK_MVIVW_CHUNK consecutive list positions in row order; the chunks
+ *      are added in chunk order.  No floating-point atomics: two runs give the same bytes.
+ *   2. d_j = sqrt(G_jj), Gs = G / (d d') with a unit diagonal; Cholesky of Gs; a squared pivot below CUSK_PHEN_PIVOT_MIN
+ *      (the bound of cusk_phen_adjust: a pivot is 1 - R^2 of an exposure on the earlier ones), or a G_jj that is not
+ *      positive, is status 2.
+ *   3. theta = D^-1 Gs^-1 D^-1 b; v_j = (Gs^-1)_jj / d_j^2.
+ *   4. rss = sum w (y - X theta)^2 in a second pass over the residuals with the same chunks (never y'Wy - theta'b, which
+ *      cancels); sigma = sqrt(rss / (m - k)).
+ *   5. se_j by model: 1 (random) sqrt(v_j) max(sigma, 1); 2 (fixed) sqrt(v_j); 0 (default) random when m >= 4, else fixed.
+ * status[a]: 0 ok; 1 k = 0 or m <= k (the reference's "sufficient_ivs" fails; nothing is computed); 2 rank deficient by
+ * the pivot rule; 3 a weight or a value of X or y among the problem's rows is NaN or infinite, or a weight is <= 0.  For
+ * status != 0 theta and se of that outcome are NaN; other outcomes of the call are not affected.
+ * Out: theta, se at the positions of ex (only [ex_off[a], ex_off[a + 1]) of every outcome is written); stats nout x 3:
+ * rss, sigma, the smallest squared pivot (status 1 and 3: NaN, NaN, NaN; status 2: NaN, NaN, the pivot that failed, 0 for
+ * a G_jj that is not positive); status nout ints.
+ * Argument errors (CUSK_ERR_ARG, message in cusk_last_error, nothing launched, nothing written): an outcome outside
+ * [0, p); an instrument outside [0, M) or an instrument list that is not strictly ascending; an exposure list that is not
+ * strictly ascending, names the outcome or names a trait outside [0, p); more than 127 exposures; offsets that are not
+ * monotone; model outside 0 .. 2; a null pointer.
+ * The chunk partials (chunks x (k + 1)(k + 2) / 2 doubles per outcome) are sized from the call; outcomes are processed in
+ * groups of at most 256 MB of partials (engine option "mvivw_part_bytes").  kernel_ms (may be NULL): device time of the kernels alone. */
+#define CUSK_MVIVW_CHUNK 256
+#define CUSK_MVIVW_MAX_EXPOSURES 127
+int cusk_mvivw(cusk_engine *e, const double *beta, const double *weight, long long M, int p, int nout, const int *outcome,
+               const long long *iv_off, const int *iv, const int *ex_off, const int *ex, int model, double *theta, double *se,
+               double *stats, int *status, float *kernel_ms);
 
 /* out_host[a*k + b] = M_dev[idx[a]*n + idx[b]]: the retained sub-matrix of parent_set.cpp:84-238
  * (reduce_gc / reduce_gcs) without copying the n*n matrix to the host; idx_host has k entries. */
