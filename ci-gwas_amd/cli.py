@@ -289,8 +289,13 @@ def _add_mvivw(sub):
     p.add_argument("--model", choices=("default", "random", "fixed"), default="default",
                    help="standard errors: random = multiplicative random effects, fixed, default = random with four or more "
                         "instruments")
+    p.add_argument("--ld", action="store_true",
+                   help="treat the instruments of an outcome as correlated: generalised least squares with the marker block of "
+                        "<cusk-output-stem>_scm.mtx as their LD; <stem>_mvivw_outcomes.tsv gains the column ld_pivot")
+    p.add_argument("--ld-ridge", metavar="L", type=TypeCheck(float, "ld-ridge", 0.0, None), default=None,
+                   help="with --ld: shrink the LD towards the identity, (1 - L) R + L I, 0 <= L < 1 (default 0)")
     p.add_argument("--out", type=str, default=None, help="output file (default <cusk-output-stem>_mvivw_results.tsv)")
-    p.set_defaults(func=run_mvivw)
+    p.set_defaults(func=run_mvivw, parser=p)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -587,11 +592,15 @@ def run_mvivw(args):
     from .ivcheck import iv_candidates, load, write_csv
 
     stem = args.cusk_output_stem
+    if args.ld_ridge is not None and not args.ld:
+        args.parser.error("--ld-ridge needs --ld")
+    if args.ld_ridge is not None and not args.ld_ridge < 1.0:
+        args.parser.error("--ld-ridge must be in [0, 1)")
     data = load(stem, het=args.het)  # unreadable inputs are reported before an engine exists; read once
     write_csv(f"{stem}_iv_candidates.csv", iv_candidates(stem, data=data))
     mode = "skeleton" if args.s else "prior" if args.orientation_prior else "ivs" if args.ivs else "all"
     res = mvivw.run(stem, args.num_samples, mode=mode, prior_path=args.orientation_prior, ivs_path=args.ivs, het=args.het,
-                    model=mvivw.MODELS[args.model], engine=_mvivw_engine(), data=data)
+                    model=mvivw.MODELS[args.model], engine=_mvivw_engine(), data=data, ld=args.ld, ld_ridge=args.ld_ridge or 0.0)
     out = args.out or f"{stem}_mvivw_results.tsv"
     mvivw.write_results(out, res)
     mvivw.write_outcomes(f"{out[:-len('_results.tsv')]}_outcomes.tsv" if out.endswith("_results.tsv") else f"{out}.outcomes.tsv", res)

@@ -190,6 +190,7 @@ struct cusk_engine
     int opt_l1_lds_row = 1;              // test hook: 0 forces the form of level1_rows2_kernel that gathers the row of C through L1/L2
     int opt_timing = 1;                  // per-level HIP events for cusk_stats' kernel_ms / level_ms (0: total only)
     long long opt_sep_ws_budget = 4ll << 30;  // HBM work space of cusk_sepselect_greedy for candidate lists beyond LDS
+    long long opt_mvivw_ld_bytes = 8ll << 30;  // HBM of cusk_mvivw_ld's m x m workspace (kLdBytes of host/mvivw_ld_plan.h)
     long long opt_mvivw_part_bytes = 256ll << 20;  // HBM of cusk_mvivw's chunk partials alive at once (kMvPartBound of host/mvivw_plan.h)
 
     // row-sharded sweep of ONE block over several engines: this engine runs the tests of rows

@@ -180,8 +180,84 @@ def solve_one(X, y, w, model: int):
     return 0, theta, se, (rss, sigma, float(minpiv))
 
 
+LD_PANEL = 64  # kLdPanel of csrc/host/mvivw_ld_plan.h
+
+
+def cholesky_ld(R):
+    """Right-looking Cholesky of the lower triangle of R (unit diagonal included) with the pivot rule, in panels of
+    LD_PANEL columns as on the device -> (status 0 | 4, C or None, smallest squared pivot | the pivot that failed)"""
+    from scipy.linalg import solve_triangular
+
+    A = np.tril(R)
+    m = A.shape[0]
+    minpiv = np.inf
+    for j0 in range(0, m, LD_PANEL):
+        j1 = min(j0 + LD_PANEL, m)
+        D = A[j0:j1, j0:j1]
+        for j in range(j1 - j0):
+            piv = D[j, j]
+            minpiv = min(minpiv, piv)
+            if not piv >= PIVOT_MIN:
+                return 4, None, float(piv)
+            D[j, j] = np.sqrt(piv)
+            D[j + 1:, j] /= D[j, j]
+            D[j + 1:, j + 1:] -= np.tril(np.outer(D[j + 1:, j], D[j + 1:, j]))
+        if j1 < m:
+            A[j1:, j0:j1] = solve_triangular(D, A[j1:, j0:j1].T, lower=True).T
+            A[j1:, j1:] -= np.tril(A[j1:, j0:j1] @ A[j1:, j0:j1].T)
+    return 0, A, float(minpiv)
+
+
+def solve_one_ld(X, y, w, R, model: int, ridge: float = 0.0):
+    """One problem of `cusk_mvivw_ld` by the rule of include/cusk_hip.h.  R: m x m, the LD of the instruments in list
+    order; its strict lower triangle is read.  -> (status, theta, se, (rss, sigma, pivot of R))"""
+    from scipy.linalg import solve_triangular
+
+    m, k = X.shape
+    nan3 = (np.nan, np.nan, np.nan)
+    if k == 0 or m <= k:
+        return 1, None, None, nan3
+    low = np.tril(np.asarray(R, np.float64), -1)
+    if not (np.isfinite(X).all() and np.isfinite(y).all() and np.isfinite(w).all() and (w > 0).all() and np.isfinite(low).all()):
+        return 3, None, None, nan3
+    st, C, rpiv = cholesky_ld(low * (1.0 - ridge) + np.eye(m))
+    if st != 0:
+        return st, None, None, (np.nan, np.nan, rpiv)
+    Zw = solve_triangular(C, np.concatenate([X, y[:, None]], axis=1) * np.sqrt(w)[:, None], lower=True)
+    st, theta, se, stat = solve_one(Zw[:, :k], Zw[:, k], np.ones(m), model)
+    return st, theta, se, ((stat[0], stat[1], rpiv) if st == 0 else stat)
+
+
 class HostEngine:
-    """`Engine.mvivw` in float64 numpy: what `mvivw(engine=None)` runs on, and the comparison form of the tests"""
+    """`Engine.mvivw` and `Engine.mvivw_ld` in float64 numpy: what `mvivw(engine=None)` runs on, and the comparison form of
+    the tests"""
+
+    def mvivw_ld(self, beta, weight, ld, outcome, iv_off, iv, ex_off, ex, model=0, ridge=0.0):
+        beta, weight, ld = np.asarray(beta, np.float64), np.asarray(weight, np.float64), np.asarray(ld, np.float64)
+        M, p = beta.shape
+        if ld.shape != (M, M):
+            raise ValueError(f"mvivw: ld is not {M} x {M}")
+        if not 0.0 <= ridge < 1.0:
+            raise ValueError("mvivw: ridge is not in [0, 1)")
+        outcome = np.asarray(outcome, np.int64).reshape(-1)
+        iv_off, ex_off = np.asarray(iv_off, np.int64).reshape(-1), np.asarray(ex_off, np.int64).reshape(-1)
+        iv, ex = np.asarray(iv, np.int64).reshape(-1), np.asarray(ex, np.int64).reshape(-1)
+        check_arguments(M, p, outcome, iv_off, iv, ex_off, ex, model)
+        nout = outcome.shape[0]
+        nex = int(ex_off.max()) if nout else 0
+        theta, se = np.full(max(nex, 1), np.nan), np.full(max(nex, 1), np.nan)
+        stats, status = np.full((nout, 3), np.nan), np.zeros(nout, np.int32)
+        for a, o in enumerate(outcome):
+            I, E = iv[iv_off[a]:iv_off[a + 1]], ex[ex_off[a]:ex_off[a + 1]]
+            if len(E) == 0 or len(I) <= len(E):
+                status[a] = 1
+                continue
+            st, th, s, stat = solve_one_ld(beta[np.ix_(I, E)], beta[I, o], weight[I, o], ld[np.ix_(I, I)], model, ridge)
+            status[a], stats[a] = st, stat
+            if st == 0:
+                theta[ex_off[a]:ex_off[a + 1]] = th
+                se[ex_off[a]:ex_off[a + 1]] = s
+        return theta, se, stats, status, 0.0
 
     def mvivw(self, beta, weight, outcome, iv_off, iv, ex_off, ex, model=0):
         beta, weight = np.asarray(beta, np.float64), np.asarray(weight, np.float64)
@@ -205,10 +281,12 @@ class HostEngine:
 
 
 def run(stem: str, num_samples: int, mode: str = "all", prior_path: str | None = None, ivs_path: str | None = None,
-        het: bool = False, model: int = 0, engine=None, data=None):
+        het: bool = False, model: int = 0, engine=None, data=None, ld: bool = False, ld_ridge: float = 0.0):
     """The estimates of every outcome of a merged skeleton.  `engine`: a device Engine (skeleton.Engine), or None for the
     numpy form.  `data`: what `ivcheck.load(stem, het)` returned.  Returns a dict: p, selection [(I, E)], theta, se (lists
-    per outcome, None unless status 0), stats, status, sk_adj (p x p bool), kernel_ms."""
+    per outcome, None unless status 0), stats, status, sk_adj (p x p bool), kernel_ms, ld.  `ld`: the instruments are taken as
+    correlated with the marker block corr[p:, p:] of the skeleton as their LD (`mvivw_ld`, ridge `ld_ridge`); stats[:, 2] is
+    then the pivot of the LD matrix and status may be 4."""
     adj, corr, p, ssz = ivcheck.load(stem, het=het) if data is None else data
     beta = np.ascontiguousarray(corr[p:, :p])
     weight = weights(beta, ssz[p:, :p] if het else num_samples)
@@ -220,12 +298,18 @@ def run(stem: str, num_samples: int, mode: str = "all", prior_path: str | None =
             raise ValueError(f"mvivw: outcome trait {o + 1} (1-based) has {len(E)} exposures; at most {MAX_EXPOSURES} are supported")
     iv_off, iv, ex_off, ex = pack(selection)
     eng = engine if engine is not None else HostEngine()
-    theta, se, stats, status, ms = eng.mvivw(beta, weight, np.arange(p, dtype=np.int32), iv_off, iv, ex_off, ex, model)
+    if ld_ridge != 0.0 and not ld:
+        raise ValueError("mvivw: ld_ridge without ld")
+    if ld:
+        theta, se, stats, status, ms = eng.mvivw_ld(beta, weight, np.ascontiguousarray(corr[p:, p:], dtype=np.float64),
+                                                    np.arange(p, dtype=np.int32), iv_off, iv, ex_off, ex, model, ridge=ld_ridge)
+    else:
+        theta, se, stats, status, ms = eng.mvivw(beta, weight, np.arange(p, dtype=np.int32), iv_off, iv, ex_off, ex, model)
     ok = [int(status[o]) == 0 for o in range(p)]
     return {"p": p, "selection": selection, "status": np.asarray(status[:p]).copy(), "stats": np.asarray(stats[:p]).copy(),
             "theta": [np.array(theta[ex_off[o]:ex_off[o + 1]]) if ok[o] else None for o in range(p)],
             "se": [np.array(se[ex_off[o]:ex_off[o + 1]]) if ok[o] else None for o in range(p)],
-            "sk_adj": np.asarray(adj)[:p, :p] != 0, "kernel_ms": ms}
+            "sk_adj": np.asarray(adj)[:p, :p] != 0, "kernel_ms": ms, "ld": bool(ld)}
 
 
 def _g(v) -> str:
@@ -245,6 +329,9 @@ def write_results(path: str, res) -> None:
             pos = {int(t): j for j, t in enumerate(E)}
             if st in (2, 3):
                 print(f"mvivw: outcome trait {o + 1} (1-based): status {st}, no estimates", file=sys.stderr)
+            elif st == 4:
+                print(f"mvivw: outcome trait {o + 1} (1-based): status 4, the LD matrix of its instruments is not positive "
+                      "definite to eight digits, no estimates; try --ld-ridge, or prune-bed at a smaller r", file=sys.stderr)
             for e in range(p):
                 if e == o:
                     continue
@@ -261,11 +348,13 @@ def write_results(path: str, res) -> None:
 
 
 def write_outcomes(path: str, res) -> None:
-    """`<stem>_mvivw_outcomes.tsv`: per outcome the heterogeneity statistic q = rss and its upper chi-square tail"""
+    """`<stem>_mvivw_outcomes.tsv`: per outcome the heterogeneity statistic q = rss and its upper chi-square tail; with
+    `--ld` a last column ld_pivot, the smallest squared pivot of the LD matrix (status 4: the pivot that failed)"""
     from scipy.stats import chi2
 
+    with_ld = bool(res.get("ld"))
     with open(path, "w") as f:
-        f.write("sink\tn_exposures\tnum_snps\tsigma\tq\tq_p\tstatus\n")
+        f.write("sink\tn_exposures\tnum_snps\tsigma\tq\tq_p\tstatus" + ("\tld_pivot" if with_ld else "") + "\n")
         for o in range(res["p"]):
             I, E = res["selection"][o]
             st = int(res["status"][o])
@@ -274,4 +363,6 @@ def write_outcomes(path: str, res) -> None:
                 cols = (_g(sigma), _g(rss), _g(float(chi2.sf(rss, len(I) - len(E)))))
             else:
                 cols = ("NA", "NA", "NA")
-            f.write(f"{o + 1}\t{len(E)}\t{len(I)}\t" + "\t".join(cols) + f"\t{st}\n")
+            piv = float(res["stats"][o][2])
+            tail = ("\t" + (_g(piv) if st in (0, 4) and np.isfinite(piv) else "NA")) if with_ld else ""
+            f.write(f"{o + 1}\t{len(E)}\t{len(I)}\t" + "\t".join(cols) + f"\t{st}{tail}\n")

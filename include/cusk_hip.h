@@ -133,7 +133,8 @@ const char *cusk_last_error(const cusk_engine *e);
  * 1: the caller guarantees it, e.g. a matrix written by cusk_corr_build), "queue_capacity" (recheck queue entries, default 4Mi), "chunk" (combination ranks per work item, default 2048), "timing" (HIP events for cusk_stats: 0 total_ms only; 1, the default, around every level's sweep: kernel_ms, and level_ms = end of the previous level's sweep to the end of this one's; 2 also level start / end: level_ms = plan to finaliser; 3 only the pair around the level-1 row kernel: main_kernel_ms[1] -- every event costs a few microseconds of device time), "chunk0" (conditioning sets per work item of the first degree class, default 512), "tmaj_min_level" (first level swept by unions T = S + Y, one inverse per l + 1 tests: default 6, 99 = never; single threshold and symmetric matrix only), "tmaj_validate_stride" (with "validate": the union-major sweep checks the unions whose per-lane count is a multiple of this power of two against double precision; default 1 = all), "hostprof" (1: host-side phase marks of every run on stderr), "max_staged_classes" (test hook: at most this many degree classes keep their sub-matrix in LDS; 0 sends every row through the kernels of the unstaged class), "chunk0_low" (work-item size of the first degree class at levels 2-4, default 256), "vec_threads" (workgroup size of the vectorised sweep for the first degree class: 64, 128 or 256; default 64), "lookahead" (levels the host enqueues ahead of the level counters it has seen, default 2; every kernel checks its level's gate on the device), "sync2" (default 1: the host reads level 2's gate record -- class counts, maximum degree -- before it enqueues that level's sweeps, so that degree classes that turn out empty are not launched at levels >= 2; 0: enqueue ahead on the level-1 degree bound), "item_capacity" (work items per degree class and level the buffers hold before the engine grows them and takes the level up again, default 1Mi), "het_filter" (default 0: cusk_run_skeleton_het / cusk_run_skeleton_batch_het run every level on the exact path; 1: their levels >= 2 go through the filter at the per-test threshold and the recheck queue like the other modes, "fast" = 0 still selects the exact path, and "validate" is accepted), "het_rows" (0 or 1, default 0: level 1 of cusk_run_skeleton_het / cusk_run_skeleton_batch_het runs on the exact sweep; 1: on the row-streaming level-1 kernel at per-pair sample sizes when "fast", "pair" and "rows" are non-zero and both C and N_dev are symmetric, N_dev bit for bit -- otherwise as with 0; same results; cusk_engine_level1_form tells which kernel ran), "sepselect_ws_bytes" (HBM work space of
  * cusk_sepselect_greedy for candidate lists too long for LDS, default 4 GiB; such pairs run in batches of what fits), "mvivw_part_bytes" (HBM of cusk_mvivw's chunk partials alive at
  * once, default 256 MiB; outcomes run in groups of what fits, an outcome that alone exceeds it as a group of its own; the
- * results do not depend on it). */
+ * results do not depend on it), "mvivw_ld_bytes" (HBM of cusk_mvivw_ld's m x m workspace, default 8 GiB; an outcome that
+ * needs more is an argument error). */
 int cusk_engine_set_option(cusk_engine *e, const char *key, long long value);
 /* Host only, no device needed: the workgroup size level 1's row-streaming kernel runs with when a row of C takes
  * row_bytes of LDS (4 (n + 8) for a single n x n matrix), or 0 when it gathers the row through the caches instead.
@@ -713,6 +714,42 @@ int cusk_iv_check_het(cusk_engine *e, const double *trait_corr, long long n, int
 int cusk_mvivw(cusk_engine *e, const double *beta, const double *weight, long long M, int p, int nout, const int *outcome,
                const long long *iv_off, const int *iv, const int *ex_off, const int *ex, int model, double *theta, double *se,
                double *stats, int *status, float *kernel_ms);
+
+/* `mvivw --ld`: the regressions of cusk_mvivw with CORRELATED instruments, by generalised least squares.  The reference
+ * foresaw it (`use_ld` of mvivw/cig_mvivw.R hands the markers' correlation block to mr_mvinput(..., correlation = ...))
+ * and hard-codes the switch off.
+ * NOT the R package: as above, MendelianRandomization can be neither run nor restated here, and nobody has checked what
+ * follows against R.  What is computed is the plain generalised-least-squares estimator
+ *   theta = (X' Om^-1 X)^-1 X' Om^-1 y,  Om = diag(s) R diag(s),  s_i = 1 / sqrt(w_i),
+ * through a Cholesky factor of R and the rule of cusk_mvivw on the whitened table.  All pointers are HOST memory; beta,
+ * weight, outcome, iv_off/iv, ex_off/ex, model and the outputs are those of cusk_mvivw.
+ *   ld     M x M doubles, row-major: the LD (correlation) of marker rows.  Only the STRICT LOWER triangle is read, and
+ *          of it only the entries ld[I_a, I_b], a > b, of an outcome's instruments; the diagonal is taken as 1
+ *   ridge  lambda in [0, 1): every off-diagonal entry read is multiplied by (1 - lambda), i.e. R_l = (1 - l) R + l I
+ * The rule per outcome, IEEE double throughout.  I = the instrument list (m rows, in list order), K = k + 1.
+ *   1. R is m x m with R_aa = 1 and R_ab = (1 - ridge) ld[max(I_a, I_b), min(I_a, I_b)] (the list ascends, so this is
+ *      ld[I_a, I_b] for a > b).
+ *   2. R = CC', C lower, right-looking.  A squared pivot that is not >= CUSK_PHEN_PIVOT_MIN (1e-8: the marker is
+ *      explained to eight digits by the earlier ones of the list) is status 4.
+ *   3. Zw = C^-1 diag(sqrt(w)) (X, y), m x K, by forward substitution.
+ *   4. On Zw the rule of cusk_mvivw, steps 1 - 5, with every weight 1: Gram sums over chunks of CUSK_MVIVW_CHUNK list
+ *      positions in row order, chunks added in chunk order; Cholesky of the unit-diagonal Gram with the 1e-8 rule (status
+ *      2); theta and v; rss = sum r^2 over r = yw - Xw theta in a second pass; sigma = sqrt(rss / (m - k)); se by model.
+ *   5. No floating-point atomics; every element of the trailing matrix of step 2 takes its updates in panel order (panels
+ *      of 64 columns, each a sum over the panel's columns in ascending order): two runs give the same bytes.
+ * status[a], in this order of precedence: 1 k = 0 or m <= k (decided on the host, nothing is computed); 3 a weight or a
+ * value of X or y among the problem's rows, or an entry of ld that step 1 reads, is NaN or infinite, or a weight is <= 0;
+ * 4 R fails the pivot rule; 2 the Gram of the whitened exposures fails it; 0 ok.  For status != 0 theta and se of the
+ * outcome are NaN; other outcomes are not affected.
+ * stats nout x 3: rss, sigma, and the smallest squared pivot of R (status 0); NaN, NaN, the pivot of R that failed
+ * (status 4); NaN, NaN, the Gram pivot that failed (status 2); NaN, NaN, NaN (status 1 and 3).
+ * Argument errors (CUSK_ERR_ARG, nothing launched, nothing written): those of cusk_mvivw; ld null; ridge outside [0, 1)
+ * or NaN; an outcome whose m * m * 8 bytes exceed engine option "mvivw_ld_bytes" (default 8 GiB), named in the message.
+ * Outcomes run one after another and share one m x m workspace; ld is copied to the device whole (M * M * 8 bytes).
+ * Cost: m^3 / 3 multiply-adds per outcome.  kernel_ms (may be NULL): device time from the first to the last kernel. */
+int cusk_mvivw_ld(cusk_engine *e, const double *beta, const double *weight, const double *ld, double ridge, long long M, int p,
+                  int nout, const int *outcome, const long long *iv_off, const int *iv, const int *ex_off, const int *ex, int model,
+                  double *theta, double *se, double *stats, int *status, float *kernel_ms);
 
 /* out_host[a*k + b] = M_dev[idx[a]*n + idx[b]]: the retained sub-matrix of parent_set.cpp:84-238
  * (reduce_gc / reduce_gcs) without copying the n*n matrix to the host; idx_host has k entries. */
