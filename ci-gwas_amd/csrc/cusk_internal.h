@@ -67,6 +67,40 @@ struct ScopedDevBuf : DevBuf
     ~ScopedDevBuf() { release(); }
 };
 
+// one call's input table: the buffer grown to hold it (never empty, so that its pointer is one) and the copy enqueued
+inline hipError_t upload_async(DevBuf &buf, const void *src, size_t bytes, hipStream_t s)
+{
+    hipError_t st = buf.ensure(bytes > 8 ? bytes : 8);
+    if (st != hipSuccess || bytes == 0) return st;
+    return hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, s);
+}
+
+// N timing events that live for one call: each is created by its first record and destroyed when the scope ends, on
+// error returns too
+template <int N>
+struct ScopedEvents
+{
+    hipEvent_t ev[N] = {};
+    ScopedEvents() = default;
+    ScopedEvents(const ScopedEvents &) = delete;
+    ScopedEvents &operator=(const ScopedEvents &) = delete;
+    ~ScopedEvents()
+    {
+        for (hipEvent_t v : ev)
+            if (v) (void)hipEventDestroy(v);
+    }
+    hipError_t record(int i, hipStream_t s)
+    {
+        if (!ev[i])
+        {
+            hipError_t st = hipEventCreate(&ev[i]);
+            if (st != hipSuccess) return st;
+        }
+        return hipEventRecord(ev[i], s);
+    }
+    hipError_t elapsed(float *ms, int i, int j) const { return hipEventElapsedTime(ms, ev[i], ev[j]); }
+};
+
 // grow-only pinned host staging; the caller names the size to allocate when `need` bytes no longer fit
 struct PinnedBuf
 {

@@ -37,18 +37,12 @@ struct LdPanel
     int tc, tr;        // grid of the trailing update (tc = 0: no trailing columns)
 };
 
-struct LdOutcome
-{
-    long long iv0;
-    int m, k;
-    int ex0, o, out;
-    int nchunks;  // chunks of kMvChunk rows of the whitened table
-};
-
 struct LdPlan
 {
     std::vector<int> status;          // per caller's outcome: 1 where nothing is computed, else 0
-    std::vector<LdOutcome> outcomes;  // the active ones, in the caller's order
+    // the active ones, in the caller's order.  One workspace serves them one after another, so every outcome's chunk
+    // partials and residual partials start at 0: part0 = 0, chunk0 = 0; nchunks counts rows of the whitened table
+    std::vector<MvOutcome> outcomes;
     int max_m = 0, max_chunks = 0;
     size_t ws_doubles = 0;  // max m * m
     size_t zt_doubles = 0;  // max (k + 1) * m
@@ -100,15 +94,9 @@ inline int mvivw_ld_plan_build(long long M, int p, int nout, const int *outcome,
                   " LD matrix needs " + std::to_string(need) + " bytes, more than mvivw_ld_bytes = " + std::to_string(ws_bytes);
             return 1;
         }
-        LdOutcome l;
-        l.iv0 = q.iv0;
-        l.m = q.m;
-        l.k = q.k;
-        l.ex0 = q.ex0;
-        l.o = q.o;
-        l.out = q.out;
-        l.nchunks = q.nchunks;
-        plan.outcomes.push_back(l);
+        plan.outcomes.push_back(q);
+        plan.outcomes.back().part0 = 0;
+        plan.outcomes.back().chunk0 = 0;
         plan.max_m = std::max(plan.max_m, q.m);
         plan.max_chunks = std::max(plan.max_chunks, q.nchunks);
         plan.ws_doubles = std::max(plan.ws_doubles, (size_t)q.m * (size_t)q.m);

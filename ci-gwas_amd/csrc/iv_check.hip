@@ -311,39 +311,23 @@ static int iv_check_impl(cusk_engine *e, const double *trait_corr, long long n, 
 
     CUSK_HIP(e, hipSetDevice(e->device));
     hipStream_t s = e->stream;
-    DevBuf d_tc, d_off, d_set, d_w, d_woff, d_status, d_slist, d_tiles, d_xs, d_order, d_thr, d_tn, d_z, d_flags;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct Release
-    {  // every return below, the error ones included, gives the buffers and events back
-        std::vector<DevBuf *> bufs;
-        hipEvent_t *ev[2];
-        ~Release()
-        {
-            for (DevBuf *d : bufs) d->release();
-            for (hipEvent_t *v : ev)
-                if (*v) (void)hipEventDestroy(*v);
-        }
-    } release{{&d_tc, &d_off, &d_set, &d_w, &d_woff, &d_status, &d_slist, &d_tiles, &d_xs, &d_order, &d_thr, &d_tn, &d_z, &d_flags},
-              {&ev0, &ev1}};
-    auto up = [&](DevBuf &b, const void *src, size_t bytes) -> hipError_t {
-        hipError_t st = b.ensure(std::max<size_t>(bytes, 8));
-        if (st != hipSuccess || bytes == 0) return st;
-        return hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s);
-    };
+    // every return below, the error ones included, gives the buffers and events back
+    ScopedDevBuf d_tc, d_off, d_set, d_w, d_woff, d_status, d_slist, d_tiles, d_xs, d_order, d_thr, d_tn, d_z, d_flags;
+    ScopedEvents<2> evs;
     const int zero_off[1] = {0};
     const size_t nset_ids = nsets ? (size_t)set_off[nsets] : 0;
-    CUSK_HIP(e, up(d_tc, trait_corr, sizeof(double) * (size_t)n * p));
-    CUSK_HIP(e, up(d_off, nsets ? set_off : zero_off, sizeof(int) * ((size_t)nsets + 1)));
-    CUSK_HIP(e, up(d_set, set, sizeof(int) * nset_ids));
-    CUSK_HIP(e, up(d_woff, plan.w_off.data(), sizeof(long long) * plan.w_off.size()));
-    CUSK_HIP(e, up(d_slist, plan.setup_sets.data(), sizeof(int) * plan.setup_sets.size()));
-    CUSK_HIP(e, up(d_tiles, plan.tiles.data(), sizeof(IvTile) * plan.tiles.size()));
-    CUSK_HIP(e, up(d_xs, plan.xs.data(), sizeof(int) * plan.xs.size()));
-    CUSK_HIP(e, up(d_order, plan.order.data(), sizeof(int) * plan.order.size()));
+    CUSK_HIP(e, upload_async(d_tc, trait_corr, sizeof(double) * (size_t)n * p, s));
+    CUSK_HIP(e, upload_async(d_off, nsets ? set_off : zero_off, sizeof(int) * ((size_t)nsets + 1), s));
+    CUSK_HIP(e, upload_async(d_set, set, sizeof(int) * nset_ids, s));
+    CUSK_HIP(e, upload_async(d_woff, plan.w_off.data(), sizeof(long long) * plan.w_off.size(), s));
+    CUSK_HIP(e, upload_async(d_slist, plan.setup_sets.data(), sizeof(int) * plan.setup_sets.size(), s));
+    CUSK_HIP(e, upload_async(d_tiles, plan.tiles.data(), sizeof(IvTile) * plan.tiles.size(), s));
+    CUSK_HIP(e, upload_async(d_xs, plan.xs.data(), sizeof(int) * plan.xs.size(), s));
+    CUSK_HIP(e, upload_async(d_order, plan.order.data(), sizeof(int) * plan.order.size(), s));
     if (het)
-        CUSK_HIP(e, up(d_tn, trait_n, sizeof(int) * (size_t)n * p));
+        CUSK_HIP(e, upload_async(d_tn, trait_n, sizeof(int) * (size_t)n * p, s));
     else  // thr[l] is read for l = a set's length, and a set an item uses leaves out the item's trait: l <= p - 1
-        CUSK_HIP(e, up(d_thr, thr, sizeof(double) * (size_t)std::min(plan.max_len + 1, p)));
+        CUSK_HIP(e, upload_async(d_thr, thr, sizeof(double) * (size_t)std::min(plan.max_len + 1, p), s));
     CUSK_HIP(e, d_w.ensure(std::max<size_t>(sizeof(double) * (size_t)plan.w_off.back(), 8)));
     CUSK_HIP(e, d_status.ensure(sizeof(int) * ((size_t)nsets + 1)));
     CUSK_HIP(e, d_z.ensure(sizeof(double) * (size_t)nitems));
@@ -366,9 +350,7 @@ static int iv_check_impl(cusk_engine *e, const double *trait_corr, long long n, 
     b.z = d_z.as<double>();
     b.flags = d_flags.as<int>();
     void (*const k_item)(IvBatch, int) = het ? iv_item_kernel<true> : iv_item_kernel<false>;
-    CUSK_HIP(e, hipEventCreate(&ev0));
-    CUSK_HIP(e, hipEventCreate(&ev1));
-    CUSK_HIP(e, hipEventRecord(ev0, s));
+    CUSK_HIP(e, evs.record(0, s));
     for (int c = 0; c < kIvClasses; c++)
     {  // LDS sized to the class (127: 129.0 KB), so a one-trait set never takes the carve of the longest one
         const size_t cnt = plan.setup_first[c + 1] - plan.setup_first[c];
@@ -393,12 +375,12 @@ static int iv_check_impl(cusk_engine *e, const double *trait_corr, long long n, 
         hipLaunchKernelGGL(k_item, dim3((unsigned)cnt), dim3(kIvTile), lds, s, b, kIvCaps[c]);
         CUSK_HIP(e, hipGetLastError());
     }
-    CUSK_HIP(e, hipEventRecord(ev1, s));
+    CUSK_HIP(e, evs.record(1, s));
     CUSK_HIP(e, hipMemcpyAsync(z, d_z.p, sizeof(double) * (size_t)nitems, hipMemcpyDeviceToHost, s));
     CUSK_HIP(e, hipMemcpyAsync(flags, d_flags.p, sizeof(int) * (size_t)nitems, hipMemcpyDeviceToHost, s));
     CUSK_HIP(e, hipStreamSynchronize(s));
     float ms = 0.0f;
-    CUSK_HIP(e, hipEventElapsedTime(&ms, ev0, ev1));
+    CUSK_HIP(e, evs.elapsed(&ms, 0, 1));
     if (kernel_ms) *kernel_ms = ms;
     return CUSK_OK;
 }

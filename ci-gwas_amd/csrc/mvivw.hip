@@ -18,46 +18,17 @@
 //                     thread, recomputed from beta and theta
 //   mv_finish_kernel  one workgroup per outcome: rss in chunk order, sigma, the standard errors by `model`
 // The host (host/mvivw_plan.h) checks every index before anything is launched.
-#include "cusk_internal.h"
-#include "host/mvivw_plan.h"
+//
+// mv_gram_kernel and mv_resid_kernel read the table; what they share with their forms for the whitened table of
+// mvivw_ld.hip (tile decode, slab walk, packed store, the ordered workgroup sum) stands in mvivw_reg.h.  mv_solve_kernel
+// and mv_finish_kernel read no table: they serve both files, through the launchers at the end of the kernels here.
+#include "mvivw_reg.h"
 
-#include <cfloat>
-#include <cmath>
-#include <limits>
 #include <string>
-#include <vector>
 
 namespace cusk {
 
 namespace {
-
-constexpr int kMvTriMax = kMvMaxExposures * (kMvMaxExposures + 1) / 2;  // 8128 doubles: 63.5 KB
-constexpr int kMvVec = 128;
-constexpr int kMvSolLd = 2 * kMvVec + 1;  // per active outcome: theta[128], v[128], the smallest squared pivot
-constexpr double kMvPivotMin = CUSK_PHEN_PIVOT_MIN;
-static_assert(kMvChunk == CUSK_MVIVW_CHUNK && kMvMaxExposures == CUSK_MVIVW_MAX_EXPOSURES, "the header states the plan's constants");
-static_assert(kMvChunk == 256, "the residual kernel gives every thread of a workgroup one row of a chunk");
-
-struct MvBatch
-{
-    const double *beta;    // M x p
-    const double *weight;  // M x p
-    int p;
-    int model;
-    const int *iv;
-    const int *ex;
-    const MvOutcome *outs;
-    double *part;     // chunk partials of the group in flight
-    int *chunk_bad;   // per chunk of the call: a value that gives status 3
-    double *rpart;    // per chunk of the call: weighted residual sum of squares
-    double *sol;      // per active outcome: kMvSolLd doubles
-    int *status;      // per active outcome
-    double *theta;    // layout of ex
-    double *se;       // layout of ex
-    double *stats;    // per active outcome: rss, sigma, smallest squared pivot
-};
-
-__device__ __forceinline__ bool mv_finite(double v) { return fabs(v) <= DBL_MAX; }  // false for NaN
 
 template <int TS, int LD, int SLAB>
 __global__ void __launch_bounds__(256) mv_gram_kernel(MvBatch b, const MvChunk *__restrict__ chunks)
@@ -71,11 +42,7 @@ __global__ void __launch_bounds__(256) mv_gram_kernel(MvBatch b, const MvChunk *
     const int k = q.k, K = k + 1, p = b.p;
     const int T = (K + TS - 1) / TS, ntiles = T * (T + 1) / 2;  // T * TS <= LD by the class table
     for (int c = tid; c < LD; c += 256) cols[c] = c < k ? b.ex[q.ex0 + c] : q.o;
-    const int t = min(tid, ntiles - 1);
-    int ti = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-    while (ti * (ti + 1) / 2 > t) ti--;
-    while ((ti + 1) * (ti + 2) / 2 <= t) ti++;
-    const int tj = t - ti * (ti + 1) / 2;
+    const int t = min(tid, ntiles - 1), ti = mv_tile_row(t), tj = t - ti * (ti + 1) / 2;
     double acc[TS][TS];
 #pragma unroll
     for (int i = 0; i < TS; i++)
@@ -103,44 +70,13 @@ __global__ void __launch_bounds__(256) mv_gram_kernel(MvBatch b, const MvChunk *
             ws[idx] = wx;
         }
         __syncthreads();
-        if (tid < ntiles)
-        {
-            const double *wa = ws + ti * TS, *zb = zs + tj * TS;
-#pragma unroll 2
-            for (int kk = 0; kk < SLAB; kk++)
-            {
-                double a[TS], c[TS];
-#pragma unroll
-                for (int i = 0; i < TS; i++) a[i] = wa[kk * LD + i];
-#pragma unroll
-                for (int j = 0; j < TS; j++) c[j] = zb[kk * LD + j];
-#pragma unroll
-                for (int i = 0; i < TS; i++)
-#pragma unroll
-                    for (int j = 0; j < TS; j++) acc[i][j] = fma(a[i], c[j], acc[i][j]);
-            }
-        }
+        if (tid < ntiles) mv_slab_walk<TS, LD, SLAB>(ws + ti * TS, zs + tj * TS, acc);
         __syncthreads();
     }
     bad = __syncthreads_or(bad);
     if (tid == 0) b.chunk_bad[q.chunk0 + ch.chunk] = bad ? 1 : 0;
-    if (tid < ntiles)
-    {
-        const int E = K * (K + 1) / 2;
-        double *dst = b.part + q.part0 + (long long)ch.chunk * E;
-#pragma unroll
-        for (int i = 0; i < TS; i++)
-#pragma unroll
-            for (int j = 0; j < TS; j++)
-            {
-                const int r = ti * TS + i, c = tj * TS + j;
-                if (r < K && c <= r) dst[r * (r + 1) / 2 + c] = acc[i][j];
-            }
-    }
+    if (tid < ntiles) mv_store_tile<TS>(b.part + q.part0 + (long long)ch.chunk * (K * (K + 1) / 2), K, ti, tj, acc);
 }
-
-// LDS carve (doubles): L[kMvTriMax], d[128], bv[128], x[128]
-constexpr size_t kMvSolveLds = sizeof(double) * ((size_t)kMvTriMax + 3 * kMvVec);
 
 __global__ void __launch_bounds__(256) mv_solve_kernel(MvBatch b, int first)
 {
@@ -154,7 +90,8 @@ __global__ void __launch_bounds__(256) mv_solve_kernel(MvBatch b, int first)
     double *x = bv + kMvVec;
     double *sol = b.sol + (size_t)slot * kMvSolLd;
     int bad = 0;
-    for (int c = tid; c < q.nchunks; c += 256) bad |= b.chunk_bad[q.chunk0 + c];
+    if (b.chunk_bad)  // null: the caller has tested the values itself
+        for (int c = tid; c < q.nchunks; c += 256) bad |= b.chunk_bad[q.chunk0 + c];
     if (__syncthreads_or(bad))
     {
         if (tid == 0)
@@ -302,12 +239,8 @@ __global__ void __launch_bounds__(256) mv_resid_kernel(MvBatch b, const MvChunk 
         const double r = b.beta[base + q.o] - fit;
         term = b.weight[base + q.o] * (r * r);
     }
-    // one order: butterflies inside each wavefront, then wavefront 0 .. 3
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) term += __shfl_xor(term, off);
-    if ((tid & 63) == 0) sh[tid >> 6] = term;
-    __syncthreads();
-    if (tid == 0) b.rpart[q.chunk0 + ch.chunk] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    const double sum = mv_block_sum(term, sh);
+    if (tid == 0) b.rpart[q.chunk0 + ch.chunk] = sum;
 }
 
 __global__ void __launch_bounds__(128) mv_finish_kernel(MvBatch b, int first)
@@ -352,6 +285,26 @@ __global__ void __launch_bounds__(128) mv_finish_kernel(MvBatch b, int first)
     }
 }
 
+}  // namespace
+
+hipError_t mv_reg_prepare()
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(mv_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)kMvSolveLds);
+}
+
+void launch_mv_solve(hipStream_t s, const MvBatch &b, int first, unsigned nslots)
+{
+    hipLaunchKernelGGL(mv_solve_kernel, dim3(nslots), dim3(256), kMvSolveLds, s, b, first);
+}
+
+void launch_mv_finish(hipStream_t s, const MvBatch &b, int first, unsigned nslots)
+{
+    hipLaunchKernelGGL(mv_finish_kernel, dim3(nslots), dim3(128), 0, s, b, first);
+}
+
+namespace {
+
 int mvivw_impl(cusk_engine *e, const double *beta, const double *weight, long long M, int p, int nout, const int *outcome,
                const long long *iv_off, const int *iv, const int *ex_off, const int *ex, int model, double *theta, double *se,
                double *stats, int *status, float *kernel_ms)
@@ -366,43 +319,23 @@ int mvivw_impl(cusk_engine *e, const double *beta, const double *weight, long lo
     if (nout > 0 && ex_off[nout] > ex_off[0] && (!theta || !se)) return fail(e, CUSK_ERR_ARG, who + ": bad arguments");
     if (kernel_ms) *kernel_ms = 0.0f;
     if (nout == 0) return CUSK_OK;
-    const double nan = std::numeric_limits<double>::quiet_NaN();
     const size_t na = plan.outcomes.size(), nex = (size_t)ex_off[nout];
-    std::vector<double> th_h(nex, nan), se_h(nex, nan), stats_h(na * 3, nan);
-    std::vector<int> st_h(na, 0);
+    MvResults res(na, nex);
     if (na > 0)
     {
         CUSK_HIP(e, hipSetDevice(e->device));
         hipStream_t s = e->stream;
-        ScopedDevBuf d_beta, d_weight, d_iv, d_ex, d_outs, d_chunks, d_part, d_bad, d_rpart, d_sol, d_status, d_theta, d_se, d_stats;
-        struct Events
-        {
-            hipEvent_t ev[2] = {nullptr, nullptr};
-            ~Events()
-            {
-                for (hipEvent_t v : ev)
-                    if (v) (void)hipEventDestroy(v);
-            }
-        } evs;
-        auto up = [&](DevBuf &buf, const void *src, size_t bytes) -> hipError_t {
-            hipError_t st = buf.ensure(std::max<size_t>(bytes, 8));
-            if (st != hipSuccess || bytes == 0) return st;
-            return hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, s);
-        };
-        CUSK_HIP(e, up(d_beta, beta, sizeof(double) * (size_t)M * p));
-        CUSK_HIP(e, up(d_weight, weight, sizeof(double) * (size_t)M * p));
-        CUSK_HIP(e, up(d_iv, iv, sizeof(int) * (size_t)iv_off[nout]));
-        CUSK_HIP(e, up(d_ex, ex, sizeof(int) * nex));
-        CUSK_HIP(e, up(d_outs, plan.outcomes.data(), sizeof(MvOutcome) * na));
-        CUSK_HIP(e, up(d_chunks, plan.chunks.data(), sizeof(MvChunk) * plan.chunks.size()));
+        ScopedDevBuf d_beta, d_weight, d_iv, d_ex, d_outs, d_chunks, d_part, d_bad, d_rpart;
+        ScopedEvents<2> evs;
+        CUSK_HIP(e, upload_async(d_beta, beta, sizeof(double) * (size_t)M * p, s));
+        CUSK_HIP(e, upload_async(d_weight, weight, sizeof(double) * (size_t)M * p, s));
+        CUSK_HIP(e, upload_async(d_iv, iv, sizeof(int) * (size_t)iv_off[nout], s));
+        CUSK_HIP(e, upload_async(d_ex, ex, sizeof(int) * nex, s));
+        CUSK_HIP(e, upload_async(d_outs, plan.outcomes.data(), sizeof(MvOutcome) * na, s));
+        CUSK_HIP(e, upload_async(d_chunks, plan.chunks.data(), sizeof(MvChunk) * plan.chunks.size(), s));
         CUSK_HIP(e, d_part.ensure(sizeof(double) * plan.max_part_doubles));
         CUSK_HIP(e, d_bad.ensure(sizeof(int) * (size_t)plan.total_chunks));
         CUSK_HIP(e, d_rpart.ensure(sizeof(double) * (size_t)plan.total_chunks));
-        CUSK_HIP(e, d_sol.ensure(sizeof(double) * na * kMvSolLd));
-        CUSK_HIP(e, d_status.ensure(sizeof(int) * na));
-        CUSK_HIP(e, d_theta.ensure(sizeof(double) * std::max<size_t>(nex, 1)));
-        CUSK_HIP(e, d_se.ensure(sizeof(double) * std::max<size_t>(nex, 1)));
-        CUSK_HIP(e, d_stats.ensure(sizeof(double) * na * 3));
 
         MvBatch b;
         b.beta = d_beta.as<double>();
@@ -415,15 +348,9 @@ int mvivw_impl(cusk_engine *e, const double *beta, const double *weight, long lo
         b.part = d_part.as<double>();
         b.chunk_bad = d_bad.as<int>();
         b.rpart = d_rpart.as<double>();
-        b.sol = d_sol.as<double>();
-        b.status = d_status.as<int>();
-        b.theta = d_theta.as<double>();
-        b.se = d_se.as<double>();
-        b.stats = d_stats.as<double>();
-        CUSK_HIP(e, hipFuncSetAttribute(reinterpret_cast<const void *>(mv_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)kMvSolveLds));
-        for (hipEvent_t &v : evs.ev) CUSK_HIP(e, hipEventCreate(&v));
-        CUSK_HIP(e, hipEventRecord(evs.ev[0], s));
+        CUSK_HIP(e, res.alloc(b));
+        CUSK_HIP(e, mv_reg_prepare());
+        CUSK_HIP(e, evs.record(0, s));
         const MvChunk *chunks = d_chunks.as<MvChunk>();
         for (const MvGroup &g : plan.groups)
         {  // one stream: the partials of a group are read before the next group's Gram kernels overwrite them
@@ -442,42 +369,30 @@ int mvivw_impl(cusk_engine *e, const double *beta, const double *weight, long lo
             }
             const unsigned nslots = (unsigned)(g.last - g.first);
             const size_t nchunks = g.class_first[kMvClasses] - g.class_first[0];
-            hipLaunchKernelGGL(mv_solve_kernel, dim3(nslots), dim3(256), kMvSolveLds, s, b, g.first);
+            launch_mv_solve(s, b, g.first, nslots);
             CUSK_HIP(e, hipGetLastError());
             hipLaunchKernelGGL(mv_resid_kernel, dim3((unsigned)nchunks), dim3(256), 0, s, b, chunks + g.class_first[0]);
             CUSK_HIP(e, hipGetLastError());
-            hipLaunchKernelGGL(mv_finish_kernel, dim3(nslots), dim3(128), 0, s, b, g.first);
+            launch_mv_finish(s, b, g.first, nslots);
             CUSK_HIP(e, hipGetLastError());
         }
-        CUSK_HIP(e, hipEventRecord(evs.ev[1], s));
-        if (nex)
-        {
-            CUSK_HIP(e, hipMemcpyAsync(th_h.data(), d_theta.p, sizeof(double) * nex, hipMemcpyDeviceToHost, s));
-            CUSK_HIP(e, hipMemcpyAsync(se_h.data(), d_se.p, sizeof(double) * nex, hipMemcpyDeviceToHost, s));
-        }
-        CUSK_HIP(e, hipMemcpyAsync(stats_h.data(), d_stats.p, sizeof(double) * na * 3, hipMemcpyDeviceToHost, s));
-        CUSK_HIP(e, hipMemcpyAsync(st_h.data(), d_status.p, sizeof(int) * na, hipMemcpyDeviceToHost, s));
+        CUSK_HIP(e, evs.record(1, s));
+        CUSK_HIP(e, res.read_back(s));
         CUSK_HIP(e, hipStreamSynchronize(s));
         float ms = 0.0f;
-        CUSK_HIP(e, hipEventElapsedTime(&ms, evs.ev[0], evs.ev[1]));
+        CUSK_HIP(e, evs.elapsed(&ms, 0, 1));
         if (kernel_ms) *kernel_ms = ms;
     }
-    // nothing of the caller's is written before this point
-    for (int a = 0; a < nout; a++)
-    {
-        status[a] = plan.status[(size_t)a];
-        for (int c = 0; c < 3; c++) stats[(size_t)a * 3 + c] = nan;
-        for (int c = ex_off[a]; c < ex_off[a + 1]; c++) theta[c] = se[c] = nan;
-    }
+    mv_fill_unset(nout, plan.status, ex_off, theta, se, stats, status);
     for (size_t slot = 0; slot < na; slot++)
     {
         const MvOutcome &q = plan.outcomes[slot];
-        status[q.out] = st_h[slot];
-        for (int c = 0; c < 3; c++) stats[(size_t)q.out * 3 + c] = stats_h[slot * 3 + c];
+        status[q.out] = res.status[slot];
+        for (int c = 0; c < 3; c++) stats[(size_t)q.out * 3 + c] = res.stats[slot * 3 + c];
         for (int c = 0; c < q.k; c++)
         {
-            theta[q.ex0 + c] = th_h[(size_t)q.ex0 + c];
-            se[q.ex0 + c] = se_h[(size_t)q.ex0 + c];
+            theta[q.ex0 + c] = res.theta[(size_t)q.ex0 + c];
+            se[q.ex0 + c] = res.se[(size_t)q.ex0 + c];
         }
     }
     return CUSK_OK;

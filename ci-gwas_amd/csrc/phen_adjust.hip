@@ -440,16 +440,6 @@ __global__ void __launch_bounds__(256) standardise_kernel(const float *__restric
 
 namespace {
 
-struct PhenEvents
-{
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~PhenEvents()
-    {
-        for (hipEvent_t v : ev)
-            if (v) (void)hipEventDestroy(v);
-    }
-};
-
 template <int NE>
 void launch_gram(dim3 grid, hipStream_t s, const float *Y, const float *X, size_t N, int c, const unsigned long long *valid,
                  const double *cstat, const int *adj_ix, size_t nchunks, double *part)
@@ -489,8 +479,7 @@ static int phen_adjust_impl(cusk_engine *e, const float *phen, const float *cova
             }
     const size_t na = adj_ix.size();
 
-    PhenEvents pe;
-    for (hipEvent_t &v : pe.ev) CUSK_HIP(e, hipEventCreate(&v));
+    ScopedEvents<6> pe;  // the marks of the five phases
 
     const float *Y = phen;
     if (!is_device_pointer(phen))
@@ -503,8 +492,7 @@ static int phen_adjust_impl(cusk_engine *e, const float *phen, const float *cova
     const float *X = covar;
     if (c > 0 && !is_device_pointer(covar))
     {
-        CUSK_HIP(e, x_buf.ensure(sizeof(float) * c * N));
-        CUSK_HIP(e, hipMemcpyAsync(x_buf.p, covar, sizeof(float) * c * N, hipMemcpyHostToDevice, s));
+        CUSK_HIP(e, upload_async(x_buf, covar, sizeof(float) * c * N, s));
         X = x_buf.as<float>();
     }
     // one allocation, in doubles: covariate and trait statistics, scaled and raw coefficients, the Grams, the chunk
@@ -527,7 +515,7 @@ static int phen_adjust_impl(cusk_engine *e, const float *phen, const float *cova
     if (na) CUSK_HIP(e, hipMemcpyAsync(adj_ix_d, adj_ix.data(), sizeof(int) * na, hipMemcpyHostToDevice, s));
     if (!moments_only) CUSK_HIP(e, out_buf.ensure(sizeof(float) * p * N));
 
-    CUSK_HIP(e, hipEventRecord(pe.ev[0], s));
+    CUSK_HIP(e, pe.record(0, s));
     if (c > 0)
     {
         hipLaunchKernelGGL(covar_valid_kernel, dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, s, X, N, c, groups, valid);
@@ -546,7 +534,7 @@ static int phen_adjust_impl(cusk_engine *e, const float *phen, const float *cova
                             std::string(name) + ": covariate " + std::to_string(j) + " is constant on the " +
                                 std::to_string((long long)cs[j * kCStat + 2]) + " individuals with every covariate observed");
     }
-    CUSK_HIP(e, hipEventRecord(pe.ev[1], s));
+    CUSK_HIP(e, pe.record(1, s));
     if (na)
     {
         const dim3 gg((unsigned)nchunks, (unsigned)na);
@@ -561,14 +549,14 @@ static int phen_adjust_impl(cusk_engine *e, const float *phen, const float *cova
             launch_gram<9>(gg, s, Y, X, N, c, valid, cstat, adj_ix_d, nchunks, part);
         CUSK_HIP(e, hipGetLastError());
     }
-    CUSK_HIP(e, hipEventRecord(pe.ev[2], s));
+    CUSK_HIP(e, pe.record(2, s));
     if (na)
     {
         hipLaunchKernelGGL(gram_reduce_kernel, dim3((unsigned)((E + 255) / 256), (unsigned)na), dim3(256), 0, s, part, nchunks, E, gram);
         hipLaunchKernelGGL(chol_solve_kernel, dim3((unsigned)na), dim3(64), 0, s, gram, c, adj_ix_d, cstat, beta_s, beta_raw, status_d);
         CUSK_HIP(e, hipGetLastError());
     }
-    CUSK_HIP(e, hipEventRecord(pe.ev[3], s));
+    CUSK_HIP(e, pe.record(3, s));
     const dim3 mg((unsigned)nchunks, (unsigned)p), fg((unsigned)((p + 63) / 64));
     const int decide = moments_only ? 0 : 1;
     hipLaunchKernelGGL(residual_moments_kernel<0>, mg, dim3(256), 0, s, Y, X, N, c, valid, cstat, flags_d, beta_s, status_d, tstat, nchunks, part);
@@ -576,13 +564,13 @@ static int phen_adjust_impl(cusk_engine *e, const float *phen, const float *cova
     hipLaunchKernelGGL(residual_moments_kernel<1>, mg, dim3(256), 0, s, Y, X, N, c, valid, cstat, flags_d, beta_s, status_d, tstat, nchunks, part);
     hipLaunchKernelGGL(moments_finish_kernel<1>, fg, dim3(64), 0, s, part, nchunks, (int)p, c, flags_d, decide, tstat, status_d);
     CUSK_HIP(e, hipGetLastError());
-    CUSK_HIP(e, hipEventRecord(pe.ev[4], s));
+    CUSK_HIP(e, pe.record(4, s));
     if (!moments_only)
     {
         hipLaunchKernelGGL(standardise_kernel, mg, dim3(256), 0, s, Y, X, N, c, valid, cstat, flags_d, beta_s, status_d, tstat, out_buf.as<float>());
         CUSK_HIP(e, hipGetLastError());
     }
-    CUSK_HIP(e, hipEventRecord(pe.ev[5], s));
+    CUSK_HIP(e, pe.record(5, s));
 
     std::vector<double> ts(p * kTStat), braw(p * k);
     std::vector<int> st(p);
@@ -591,7 +579,7 @@ static int phen_adjust_impl(cusk_engine *e, const float *phen, const float *cova
     if (na) CUSK_HIP(e, hipMemcpyAsync(braw.data(), beta_raw, sizeof(double) * braw.size(), hipMemcpyDeviceToHost, s));
     if (!moments_only) CUSK_HIP(e, hipMemcpyAsync(out_host, out_buf.p, sizeof(float) * p * N, hipMemcpyDeviceToHost, s));
     CUSK_HIP(e, hipStreamSynchronize(s));
-    for (int q = 0; q < 5; q++) CUSK_HIP(e, hipEventElapsedTime(&e->phen_ms[q], pe.ev[q], pe.ev[q + 1]));
+    for (int q = 0; q < 5; q++) CUSK_HIP(e, pe.elapsed(&e->phen_ms[q], q, q + 1));
 
     const double nan = std::numeric_limits<double>::quiet_NaN();
     for (size_t t = 0; t < p; t++)

@@ -261,25 +261,21 @@ int sepselect_greedy_impl(cusk_engine *e, const double *trait_corr, long long n,
 
     CUSK_HIP(e, hipSetDevice(e->device));
     hipStream_t s = e->stream;
-    DevBuf d_tc, d_pi, d_pj, d_pc, d_off, d_cand, d_thr, d_tn, d_pn, d_sel, d_len, d_flags, d_list, d_ws;
-    auto up = [&](DevBuf &b, const void *src, size_t bytes) -> hipError_t {
-        hipError_t st = b.ensure(std::max<size_t>(bytes, 8));
-        if (st != hipSuccess || bytes == 0) return st;
-        return hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s);
-    };
-    CUSK_HIP(e, up(d_tc, trait_corr, sizeof(double) * (size_t)n * p));
-    CUSK_HIP(e, up(d_pi, pair_i, sizeof(int) * (size_t)npairs));
-    CUSK_HIP(e, up(d_pj, pair_j, sizeof(int) * (size_t)npairs));
-    CUSK_HIP(e, up(d_pc, pair_corr, sizeof(double) * (size_t)npairs));
-    CUSK_HIP(e, up(d_off, cand_off, sizeof(long long) * (size_t)(npairs + 1)));
-    CUSK_HIP(e, up(d_cand, cand, sizeof(int) * (size_t)total));
+    ScopedDevBuf d_tc, d_pi, d_pj, d_pc, d_off, d_cand, d_thr, d_tn, d_pn, d_sel, d_len, d_flags, d_list, d_ws;
+    ScopedEvents<2> evs;
+    CUSK_HIP(e, upload_async(d_tc, trait_corr, sizeof(double) * (size_t)n * p, s));
+    CUSK_HIP(e, upload_async(d_pi, pair_i, sizeof(int) * (size_t)npairs, s));
+    CUSK_HIP(e, upload_async(d_pj, pair_j, sizeof(int) * (size_t)npairs, s));
+    CUSK_HIP(e, upload_async(d_pc, pair_corr, sizeof(double) * (size_t)npairs, s));
+    CUSK_HIP(e, upload_async(d_off, cand_off, sizeof(long long) * (size_t)(npairs + 1), s));
+    CUSK_HIP(e, upload_async(d_cand, cand, sizeof(int) * (size_t)total, s));
     if (het)
     {
-        CUSK_HIP(e, up(d_tn, trait_n, sizeof(int) * (size_t)n * p));
-        CUSK_HIP(e, up(d_pn, pair_n, sizeof(int) * (size_t)npairs));
+        CUSK_HIP(e, upload_async(d_tn, trait_n, sizeof(int) * (size_t)n * p, s));
+        CUSK_HIP(e, upload_async(d_pn, pair_n, sizeof(int) * (size_t)npairs, s));
     }
     else
-        CUSK_HIP(e, up(d_thr, thr, sizeof(double) * (size_t)nthr));
+        CUSK_HIP(e, upload_async(d_thr, thr, sizeof(double) * (size_t)nthr, s));
     CUSK_HIP(e, d_sel.ensure(std::max<size_t>(sizeof(int) * (size_t)total, 8)));
     CUSK_HIP(e, d_len.ensure(sizeof(int) * (size_t)npairs));
     CUSK_HIP(e, d_flags.ensure(sizeof(int) * (size_t)npairs));
@@ -292,7 +288,7 @@ int sepselect_greedy_impl(cusk_engine *e, const double *trait_corr, long long n,
         flat.insert(flat.end(), lists[c].begin(), lists[c].end());
     }
     first[kSepLdsClasses + 1] = flat.size();
-    CUSK_HIP(e, up(d_list, flat.data(), sizeof(int) * flat.size()));
+    CUSK_HIP(e, upload_async(d_list, flat.data(), sizeof(int) * flat.size(), s));
     const size_t nbig = lists[kSepLdsClasses].size();
     const size_t big_bytes = (sep_bytes(max_t) + 15) & ~(size_t)15;
     // the HBM work space of the long-list pairs is bounded: they run in batches of what fits into the budget (option
@@ -319,10 +315,7 @@ int sepselect_greedy_impl(cusk_engine *e, const double *trait_corr, long long n,
     b.ws_stride = (long long)(big_bytes / sizeof(double));
     void (*const k_lds)(SepBatch, int) = het ? sepselect_kernel<true, true> : sepselect_kernel<true, false>;
     void (*const k_hbm)(SepBatch, int) = het ? sepselect_kernel<false, true> : sepselect_kernel<false, false>;
-    hipEvent_t ev0, ev1;
-    CUSK_HIP(e, hipEventCreate(&ev0));
-    CUSK_HIP(e, hipEventCreate(&ev1));
-    CUSK_HIP(e, hipEventRecord(ev0, s));
+    CUSK_HIP(e, evs.record(0, s));
     for (int c = 0; c <= kSepLdsClasses; c++)
     {
         const size_t cnt = first[c + 1] - first[c];
@@ -347,17 +340,14 @@ int sepselect_greedy_impl(cusk_engine *e, const double *trait_corr, long long n,
         }
         CUSK_HIP(e, hipGetLastError());
     }
-    CUSK_HIP(e, hipEventRecord(ev1, s));
+    CUSK_HIP(e, evs.record(1, s));
     if (total) CUSK_HIP(e, hipMemcpyAsync(sel, d_sel.p, sizeof(int) * (size_t)total, hipMemcpyDeviceToHost, s));
     CUSK_HIP(e, hipMemcpyAsync(sel_len, d_len.p, sizeof(int) * (size_t)npairs, hipMemcpyDeviceToHost, s));
     CUSK_HIP(e, hipMemcpyAsync(flags, d_flags.p, sizeof(int) * (size_t)npairs, hipMemcpyDeviceToHost, s));
     CUSK_HIP(e, hipStreamSynchronize(s));
     float ms = 0.0f;
-    CUSK_HIP(e, hipEventElapsedTime(&ms, ev0, ev1));
+    CUSK_HIP(e, evs.elapsed(&ms, 0, 1));
     if (kernel_ms) *kernel_ms = ms;
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
-    for (DevBuf *d : {&d_tc, &d_pi, &d_pj, &d_pc, &d_off, &d_cand, &d_thr, &d_tn, &d_pn, &d_sel, &d_len, &d_flags, &d_list, &d_ws}) d->release();
     return CUSK_OK;
 }
 

@@ -232,13 +232,10 @@ class HostEngine:
     """`Engine.mvivw` and `Engine.mvivw_ld` in float64 numpy: what `mvivw(engine=None)` runs on, and the comparison form of
     the tests"""
 
-    def mvivw_ld(self, beta, weight, ld, outcome, iv_off, iv, ex_off, ex, model=0, ridge=0.0):
-        beta, weight, ld = np.asarray(beta, np.float64), np.asarray(weight, np.float64), np.asarray(ld, np.float64)
+    @staticmethod
+    def _run(beta, weight, outcome, iv_off, iv, ex_off, ex, model, solve):
+        """The batch both methods walk; `solve(I, E, o)` -> (status, theta, se, stats) of one outcome (solve_one's)"""
         M, p = beta.shape
-        if ld.shape != (M, M):
-            raise ValueError(f"mvivw: ld is not {M} x {M}")
-        if not 0.0 <= ridge < 1.0:
-            raise ValueError("mvivw: ridge is not in [0, 1)")
         outcome = np.asarray(outcome, np.int64).reshape(-1)
         iv_off, ex_off = np.asarray(iv_off, np.int64).reshape(-1), np.asarray(ex_off, np.int64).reshape(-1)
         iv, ex = np.asarray(iv, np.int64).reshape(-1), np.asarray(ex, np.int64).reshape(-1)
@@ -248,36 +245,27 @@ class HostEngine:
         theta, se = np.full(max(nex, 1), np.nan), np.full(max(nex, 1), np.nan)
         stats, status = np.full((nout, 3), np.nan), np.zeros(nout, np.int32)
         for a, o in enumerate(outcome):
-            I, E = iv[iv_off[a]:iv_off[a + 1]], ex[ex_off[a]:ex_off[a + 1]]
-            if len(E) == 0 or len(I) <= len(E):
-                status[a] = 1
-                continue
-            st, th, s, stat = solve_one_ld(beta[np.ix_(I, E)], beta[I, o], weight[I, o], ld[np.ix_(I, I)], model, ridge)
+            st, th, s, stat = solve(iv[iv_off[a]:iv_off[a + 1]], ex[ex_off[a]:ex_off[a + 1]], o)
             status[a], stats[a] = st, stat
             if st == 0:
                 theta[ex_off[a]:ex_off[a + 1]] = th
                 se[ex_off[a]:ex_off[a + 1]] = s
         return theta, se, stats, status, 0.0
 
+    def mvivw_ld(self, beta, weight, ld, outcome, iv_off, iv, ex_off, ex, model=0, ridge=0.0):
+        beta, weight, ld = np.asarray(beta, np.float64), np.asarray(weight, np.float64), np.asarray(ld, np.float64)
+        M = beta.shape[0]
+        if ld.shape != (M, M):
+            raise ValueError(f"mvivw: ld is not {M} x {M}")
+        if not 0.0 <= ridge < 1.0:
+            raise ValueError("mvivw: ridge is not in [0, 1)")
+        return self._run(beta, weight, outcome, iv_off, iv, ex_off, ex, model, lambda I, E, o: solve_one_ld(
+            beta[np.ix_(I, E)], beta[I, o], weight[I, o], ld[np.ix_(I, I)], model, ridge))
+
     def mvivw(self, beta, weight, outcome, iv_off, iv, ex_off, ex, model=0):
         beta, weight = np.asarray(beta, np.float64), np.asarray(weight, np.float64)
-        M, p = beta.shape
-        outcome = np.asarray(outcome, np.int64).reshape(-1)
-        iv_off, ex_off = np.asarray(iv_off, np.int64).reshape(-1), np.asarray(ex_off, np.int64).reshape(-1)
-        iv, ex = np.asarray(iv, np.int64).reshape(-1), np.asarray(ex, np.int64).reshape(-1)
-        check_arguments(M, p, outcome, iv_off, iv, ex_off, ex, model)
-        nout = outcome.shape[0]
-        nex = int(ex_off.max()) if nout else 0
-        theta, se = np.full(max(nex, 1), np.nan), np.full(max(nex, 1), np.nan)
-        stats, status = np.full((nout, 3), np.nan), np.zeros(nout, np.int32)
-        for a, o in enumerate(outcome):
-            I, E = iv[iv_off[a]:iv_off[a + 1]], ex[ex_off[a]:ex_off[a + 1]]
-            st, th, s, stat = solve_one(beta[np.ix_(I, E)], beta[I, o], weight[I, o], model)
-            status[a], stats[a] = st, stat
-            if st == 0:
-                theta[ex_off[a]:ex_off[a + 1]] = th
-                se[ex_off[a]:ex_off[a + 1]] = s
-        return theta, se, stats, status, 0.0
+        return self._run(beta, weight, outcome, iv_off, iv, ex_off, ex, model, lambda I, E, o: solve_one(
+            beta[np.ix_(I, E)], beta[I, o], weight[I, o], model))
 
 
 def run(stem: str, num_samples: int, mode: str = "all", prior_path: str | None = None, ivs_path: str | None = None,

@@ -875,16 +875,13 @@ class Engine:
                                             _ptr(z), _ptr(flags), _ptr(ms)))
         return z[:nitems], flags[:nitems], float(ms[0])
 
-    def mvivw(self, beta, weight, outcome, iv_off, iv, ex_off, ex, model=0, theta=None, se=None, stats=None, status=None):
-        """Multivariable IVW regressions of a batch of outcomes (cusk_mvivw; the rule is stated in include/cusk_hip.h):
-        `beta`, `weight` M x p float64, `iv[iv_off[a]:iv_off[a + 1]]` the ascending instrument rows and
-        `ex[ex_off[a]:ex_off[a + 1]]` the ascending exposure traits of outcome a.  Returns (theta, se, stats, status,
-        kernel_ms): theta and se at the positions of `ex`, stats nout x 3 (rss, sigma, smallest squared pivot).  The four
-        output arrays may be given to be filled in place."""
+    @staticmethod
+    def _mvivw_args(beta, weight, outcome, iv_off, iv, ex_off, ex, theta, se, stats, status):
+        """The arguments `mvivw` and `mvivw_ld` share, as contiguous arrays of the ABI's types, and the four output arrays
+        (the caller's, or new ones) -> (beta, weight, outcome, iv_off, iv, ex_off, ex, theta, se, stats, status)"""
         beta = np.ascontiguousarray(beta, np.float64)
         weight = np.ascontiguousarray(weight, np.float64)
         assert beta.ndim == 2 and weight.shape == beta.shape
-        M, p = beta.shape
         outcome = np.ascontiguousarray(outcome, np.int32).reshape(-1)
         iv_off = np.ascontiguousarray(iv_off, np.int64).reshape(-1)
         ex_off = np.ascontiguousarray(ex_off, np.int32).reshape(-1)
@@ -901,6 +898,17 @@ class Engine:
         assert theta.dtype == np.float64 and se.dtype == np.float64 and stats.dtype == np.float64 and status.dtype == np.int32
         assert theta.shape[0] >= nex and se.shape[0] >= nex and stats.size >= 3 * nout and status.shape[0] >= nout
         assert all(a.flags.c_contiguous for a in (theta, se, stats, status))
+        return beta, weight, outcome, iv_off, iv, ex_off, ex, theta, se, stats, status
+
+    def mvivw(self, beta, weight, outcome, iv_off, iv, ex_off, ex, model=0, theta=None, se=None, stats=None, status=None):
+        """Multivariable IVW regressions of a batch of outcomes (cusk_mvivw; the rule is stated in include/cusk_hip.h):
+        `beta`, `weight` M x p float64, `iv[iv_off[a]:iv_off[a + 1]]` the ascending instrument rows and
+        `ex[ex_off[a]:ex_off[a + 1]]` the ascending exposure traits of outcome a.  Returns (theta, se, stats, status,
+        kernel_ms): theta and se at the positions of `ex`, stats nout x 3 (rss, sigma, smallest squared pivot).  The four
+        output arrays may be given to be filled in place."""
+        beta, weight, outcome, iv_off, iv, ex_off, ex, theta, se, stats, status = self._mvivw_args(
+            beta, weight, outcome, iv_off, iv, ex_off, ex, theta, se, stats, status)
+        (M, p), nout = beta.shape, outcome.shape[0]
         ms = np.zeros(1, np.float32)
         self._check(lib().cusk_mvivw(self.h, _ptr(beta), _ptr(weight), M, p, nout, _ptr(outcome), _ptr(iv_off), _ptr(iv),
                                      _ptr(ex_off), _ptr(ex), int(model), _ptr(theta), _ptr(se), _ptr(stats), _ptr(status),
@@ -913,28 +921,11 @@ class Engine:
         include/cusk_hip.h): `ld` M x M float64, of which the strict lower triangle is read, `ridge` in [0, 1).  The other
         arguments and the return value are those of `mvivw`; stats[:, 2] is the smallest squared pivot of the LD matrix
         (status 0) or the pivot that failed (status 4)."""
-        beta = np.ascontiguousarray(beta, np.float64)
-        weight = np.ascontiguousarray(weight, np.float64)
+        beta, weight, outcome, iv_off, iv, ex_off, ex, theta, se, stats, status = self._mvivw_args(
+            beta, weight, outcome, iv_off, iv, ex_off, ex, theta, se, stats, status)
+        (M, p), nout = beta.shape, outcome.shape[0]
         ld = np.ascontiguousarray(ld, np.float64)
-        assert beta.ndim == 2 and weight.shape == beta.shape
-        M, p = beta.shape
         assert ld.shape == (M, M)
-        outcome = np.ascontiguousarray(outcome, np.int32).reshape(-1)
-        iv_off = np.ascontiguousarray(iv_off, np.int64).reshape(-1)
-        ex_off = np.ascontiguousarray(ex_off, np.int32).reshape(-1)
-        iv = np.ascontiguousarray(iv, np.int32).reshape(-1)
-        ex = np.ascontiguousarray(ex, np.int32).reshape(-1)
-        nout = outcome.shape[0]
-        assert iv_off.shape[0] == nout + 1 and ex_off.shape[0] == nout + 1
-        assert iv.shape[0] >= int(iv_off.max()) and ex.shape[0] >= int(ex_off.max())
-        nex = max(int(ex_off.max()), 1)
-        theta = np.full(nex, np.nan) if theta is None else theta
-        se = np.full(nex, np.nan) if se is None else se
-        stats = np.full((max(nout, 1), 3), np.nan) if stats is None else stats
-        status = np.zeros(max(nout, 1), np.int32) if status is None else status
-        assert theta.dtype == np.float64 and se.dtype == np.float64 and stats.dtype == np.float64 and status.dtype == np.int32
-        assert theta.shape[0] >= nex and se.shape[0] >= nex and stats.size >= 3 * nout and status.shape[0] >= nout
-        assert all(a.flags.c_contiguous for a in (theta, se, stats, status))
         ms = np.zeros(1, np.float32)
         self._check(lib().cusk_mvivw_ld(self.h, _ptr(beta), _ptr(weight), _ptr(ld), float(ridge), M, p, nout, _ptr(outcome),
                                         _ptr(iv_off), _ptr(iv), _ptr(ex_off), _ptr(ex), int(model), _ptr(theta), _ptr(se),

@@ -149,6 +149,9 @@ static void arguments()
     CHECK(mvivw_ld_plan_build(M, p, 2, outcome, iv_off, iv.data(), ex_off, ex.data(), 0, 0.0, kLdBytes, plan, msg) == 0);
     CHECK(plan.outcomes.size() == 2 && plan.ws_doubles == 600u * 600u && plan.zt_doubles == 4u * 600u && plan.max_chunks == 3);
     CHECK(plan.outcomes[1].iv0 == 600 && plan.outcomes[1].m == 300 && plan.outcomes[1].k == 2 && plan.outcomes[1].ex0 == 3);
+    // the outcomes are those of cusk_mvivw's plan, each at the start of the one workspace
+    CHECK(plan.outcomes[0].nchunks == 3 && plan.outcomes[1].nchunks == 2 && plan.outcomes[1].o == 5 && plan.outcomes[1].out == 1);
+    for (const MvOutcome &q : plan.outcomes) CHECK(q.part0 == 0 && q.chunk0 == 0);
     // the bound: exactly m * m * 8 fits, one byte less does not, and the message names the outcome
     CHECK(mvivw_ld_plan_build(M, p, 2, outcome, iv_off, iv.data(), ex_off, ex.data(), 0, 0.0, 600ll * 600 * 8, plan, msg) == 0);
     CHECK(mvivw_ld_plan_build(M, p, 2, outcome, iv_off, iv.data(), ex_off, ex.data(), 0, 0.0, 600ll * 600 * 8 - 1, plan, msg) == 1);
