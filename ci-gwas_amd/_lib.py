@@ -148,6 +148,9 @@ SYMBOLS = {
     "cusk_phen_adjust": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cusk_phen_moments": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "cusk_phen_timing": (None, [_vp, _vp]),
+    "cusk_phen_rint": (_i, [_vp, _vp, _sz, _sz, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cusk_phen_rint_timing": (None, [_vp, _vp]),
+    "cusk_phen_rint_tile": (_sz, []),
     "cusk_phen_table_load": (_i, [C.POINTER(_vp), C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
     "cusk_phen_table_rows": (_sz, [_vp]),
     "cusk_phen_table_cols": (_sz, [_vp]),

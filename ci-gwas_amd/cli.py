@@ -17,7 +17,8 @@ decided on the device, on the banded Kendall-npn correlation that `block` and th
 loader takes the rows of the .phen as they come.  `prep-phen BFILES TABLE OUT [--covar FILE] [--ordinal NAMES]` matches a
 trait table to the .fam by IID, removes the covariates from every trait by least squares (never from an ordinal one: a
 residual has no levels) and standardises to mean 0 and population sd 1 over the observed values, on the device (`mps
-prep-phen`; the rule is stated in include/cusk_hip.h).  `check-phen BFILES PHEN` reports whether an existing .phen is
+prep-phen`; the rule is stated in include/cusk_hip.h).  `--rint [--rint-offset C]` then replaces every trait that is not
+ordinal by the normal scores of its average ranks (cusk_phen_rint).  `check-phen BFILES PHEN` reports whether an existing .phen is
 row-aligned and standardised and exits 1 if not.
 Two more things the reference leaves to the user: `sumstats` writes the three correlation files of `cuskss` from a
 PLINK set and a .phen, and `cuskss-merged --bfiles --phen` runs the merged step straight from those.  For phenotypes
@@ -136,6 +137,12 @@ def _add_prep_phen(sub):
     p.add_argument("--ordinal", type=str, default=None, metavar="NAMES",
                    help="comma-separated names (or 1-based numbers) of the traits that are ordinal, as `sumstats --ordinal` "
                         "takes them: standardised only, never residualised (a residual has no levels)")
+    p.add_argument("--rint", action="store_true",
+                   help="rank-based inverse normal transform of every trait that is not ordinal, taken on the float32 "
+                        "standardised residuals: average ranks for ties, normal scores of (rank - C) / (n + 1 - 2 C), "
+                        "standardised again")
+    p.add_argument("--rint-offset", type=float, default=None, metavar="C",
+                   help="with --rint: the offset C in [0, 0.5] (default 0.375, Blom)")
     p.set_defaults(func=prep_phen)
     p = sub.add_parser("check-phen", help="Report whether a .phen is row-aligned to the .fam and standardised; exit status 1 "
                                           "if not (requires GPU)")
@@ -429,8 +436,13 @@ def _same_path(a: str, b: str) -> bool:
 
 
 def prep_phen_argv(args) -> list[str]:
-    """`mps prep-phen <bfiles> <table> <out> <covar|NULL> [ordinal=<1-based,...>]`"""
+    """`mps prep-phen <bfiles> <table> <out> <covar|NULL> [ordinal=<1-based,...>] [rint|rint=<offset>]`"""
     covar = getattr(args, "covar", None)
+    rint, offset = getattr(args, "rint", False), getattr(args, "rint_offset", None)
+    if offset is not None and not rint:
+        sys.exit("prep-phen: --rint-offset needs --rint.")
+    if offset is not None and not 0.0 <= offset <= 0.5:  # false for NaN too
+        sys.exit(f"prep-phen: --rint-offset {offset} is not in [0, 0.5].")
     if _same_path(args.out, args.table):
         sys.exit("prep-phen: OUT must differ from TABLE.")
     if covar is not None and _same_path(args.out, covar):
@@ -439,7 +451,8 @@ def prep_phen_argv(args) -> list[str]:
         sys.exit("prep-phen: OUT must differ from the .fam.")
     ordinal = getattr(args, "ordinal", None)
     return [MPS_PATH, "prep-phen", args.bfiles, args.table, args.out, covar if covar is not None else "NULL"] + (
-        [ordinal_arg("prep-phen", ordinal, args.table)] if ordinal is not None else [])
+        [ordinal_arg("prep-phen", ordinal, args.table)] if ordinal is not None else []) + (
+        ["rint" if offset is None else f"rint={offset!r}"] if rint else [])
 
 
 def check_phen_argv(args) -> list[str]:

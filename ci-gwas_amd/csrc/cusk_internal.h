@@ -226,6 +226,7 @@ struct cusk_engine
     long long opt_sep_ws_budget = 4ll << 30;  // HBM work space of cusk_sepselect_greedy for candidate lists beyond LDS
     long long opt_mvivw_ld_bytes = 8ll << 30;  // HBM of cusk_mvivw_ld's m x m workspace (kLdBytes of host/mvivw_ld_plan.h)
     long long opt_mvivw_part_bytes = 256ll << 20;  // HBM of cusk_mvivw's chunk partials alive at once (kMvPartBound of host/mvivw_plan.h)
+    long long opt_phen_rint_bytes = 1ll << 30;  // HBM of cusk_phen_rint's keys and ranks alive at once: traits run in groups of what fits
 
     // row-sharded sweep of ONE block over several engines: this engine runs the tests of rows
     // X with X % shard_world == shard_rank and joins the others through an element-wise unsigned MIN of the
@@ -248,6 +249,7 @@ struct cusk_engine
     float ord_ms[3] = {0, 0, 0};  // cusk_ordinal_timing: table kernel, polychoric fit kernel, polyserial fit kernel of their last calls
     hipEvent_t ev_prune[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // its phase marks, created by the first cusk_ld_prune
     float phen_ms[5] = {0, 0, 0, 0, 0};  // cusk_phen_timing: scaling, Gram, solve, moments, standardise of the last cusk_phen_adjust
+    float rint_ms[4] = {0, 0, 0, 0};     // cusk_phen_rint_timing: keys, sort, ranks, moments + standardise of the last cusk_phen_rint
 };
 
 namespace cusk {

@@ -18,7 +18,7 @@ namespace {
 const char *PREP_PHEN_USAGE = R"(
 Match a trait table to the .fam, remove covariates from the traits and standardise them
 
-usage: mps prep-phen <bfiles> <table> <out> <covar|NULL> [ordinal=<1-based,...>]
+usage: mps prep-phen <bfiles> <table> <out> <covar|NULL> [ordinal=<1-based,...>] [rint|rint=<offset>]
 
 arguments:
     bfiles          stem of .bed, .bim, .fam fileset; only the .fam is read
@@ -26,10 +26,14 @@ arguments:
     out             the .phen to write: one row per individual of the .fam, in its order; <out>.prep.tsv beside it
     covar           covariate table in the format of the trait table (at most 63 numeric columns), or NULL
     ordinal=...     1-based numbers of the traits that are ordinal: standardised only, never residualised
+    rint            rank-based inverse normal transform of every trait that is not ordinal, behind the step above;
+                    rint=<offset> sets the offset c of (rank - c) / (n + 1 - 2c), 0 <= c <= 0.5 (default 0.375, Blom)
 
 Every trait is regressed on the covariates (with an intercept) over the individuals that have the trait and every covariate,
 and the residuals are standardised to mean 0 and population standard deviation 1; without covariates, and for ordinal traits,
 the values themselves are.  Individuals without the trait (or, for an adjusted trait, without a covariate) get NA.
+With rint the ranks are taken on those standardised residuals as float32, the values the file would hold without it: ties
+get their average rank, the normal scores are standardised again, and <out>.prep.tsv gains the columns rint_mean rint_sd.
 )";
 
 const char *CHECK_PHEN_USAGE = R"(
@@ -71,7 +75,22 @@ int host::cmd_prep_phen(int argc, char **argv)
     const std::string bfiles = argv[2], table_path = argv[3], out_path = argv[4], covar_path = argv[5];
     bool with_ordinal = false;
     std::string ordinal_arg;
-    parse_trailing_words("prep-phen", argc, argv, 6, {{"ordinal=", 0, &with_ordinal, &ordinal_arg}});
+    bool rint_word = false, rint_offset_word = false;
+    std::string rint_arg;
+    parse_trailing_words("prep-phen", argc, argv, 6,
+                         {{"ordinal=", 0, &with_ordinal, &ordinal_arg},
+                          {"rint", TrailingWord::kFree, &rint_word, nullptr},
+                          {"rint=", TrailingWord::kFree, &rint_offset_word, &rint_arg}});
+    if (rint_word && rint_offset_word) die("prep-phen: give rint or rint=<offset>, not both");
+    const bool with_rint = rint_word || rint_offset_word;
+    double rint_offset = 0.375;
+    if (rint_offset_word)
+    {
+        const std::string tok = rint_arg.substr(5);
+        char *end = nullptr;
+        rint_offset = std::strtod(tok.c_str(), &end);
+        if (tok.empty() || *end != '\0' || !(rint_offset >= 0.0 && rint_offset <= 0.5)) die("prep-phen: rint offset '" + tok + "' is not a number in [0, 0.5]");
+    }
     const bool with_covar = covar_path != "NULL";
     const std::string fam_path = bfiles + ".fam";
     check_path(fam_path);
@@ -98,7 +117,7 @@ int host::cmd_prep_phen(int argc, char **argv)
     }
     tm.mark("read and align tables");
     const size_t p = Y.p(), c = X.p(), N = fam.n();
-    std::vector<unsigned char> adjust(p, with_covar ? 1 : 0);
+    std::vector<unsigned char> adjust(p, with_covar ? 1 : 0), transform(p, with_rint ? 1 : 0);
     if (with_ordinal)
     {
         std::istringstream ss(ordinal_arg.substr(ordinal_arg.find('=') + 1));
@@ -110,6 +129,7 @@ int host::cmd_prep_phen(int argc, char **argv)
             const long v = std::strtol(tok.c_str(), &end, 10);
             if (tok.empty() || *end != '\0' || v < 1 || (size_t)v > p) die("prep-phen: ordinal trait number '" + tok + "' is not in 1 .. " + std::to_string(p));
             adjust[(size_t)v - 1] = 0;
+            transform[(size_t)v - 1] = 0;
             ++listed;
         }
         if (listed == 0) die("prep-phen: ordinal= without trait numbers");
@@ -141,7 +161,6 @@ int host::cmd_prep_phen(int argc, char **argv)
         std::cout << "[t] device: scaling " << ms[0] << " ms, gram " << ms[1] << " ms, solve " << ms[2] << " ms, moments " << ms[3]
                   << " ms, standardise " << ms[4] << " ms" << std::endl;
     }
-    cusk_engine_destroy(e);
     tm.mark("adjust and standardise (device, with copies)");
     std::string refused;
     for (size_t t = 0; t < p; t++)
@@ -150,14 +169,41 @@ int host::cmd_prep_phen(int argc, char **argv)
                        (status[t] == CUSK_PHEN_SINGULAR
                             ? "the covariates are collinear on the " + std::to_string(n[t]) + " individuals that have this trait"
                             : "too few individuals (" + std::to_string(n[t]) + ") or no variation");
+    // the transform of what the file would hold without it; a trait refused above is already named
+    std::vector<double> rint_mean(p), rint_sd(p);
+    if (with_rint && refused.empty())
+    {
+        std::vector<float> scores(p * N);
+        std::vector<int> rint_n(p), rint_status(p);
+        if (cusk_phen_rint(e, out.data(), N, p, transform.data(), rint_offset, scores.data(), rint_n.data(), rint_mean.data(), rint_sd.data(),
+                           rint_status.data(), nullptr) != CUSK_OK)
+            engine_die("prep-phen", e);
+        if (tm.on)
+        {
+            float ms[4];
+            cusk_phen_rint_timing(e, ms);
+            std::cout << "[t] device: rint keys " << ms[0] << " ms, sort " << ms[1] << " ms, ranks " << ms[2] << " ms, moments and standardise "
+                      << ms[3] << " ms" << std::endl;
+        }
+        for (size_t t = 0; t < p; t++)
+            if (rint_status[t] != CUSK_PHEN_OK)
+                refused += "\n  " + Y.names[t] + ": too few individuals (" + std::to_string(rint_n[t]) + ") or no variation to rank";
+        out.swap(scores);
+        tm.mark("rank-based inverse normal transform (device, with copies)");
+    }
+    cusk_engine_destroy(e);
     if (!refused.empty()) die("prep-phen: nothing written; these traits cannot be prepared:" + refused);
 
     write_phen_file(out_path, fam, Y.names, out.data());
     CheckedTextFile rep(out_path + ".prep.tsv");
-    std::string text = "trait\tmode\tn\tmean\tsd\tr2\n";
+    std::string text = std::string("trait\tmode\tn\tmean\tsd\tr2") + (with_rint ? "\trint_mean\trint_sd" : "") + "\n";
     for (size_t t = 0; t < p; t++)
-        text += Y.names[t] + "\t" + (adjust[t] ? "adjusted" : "standardised") + "\t" + std::to_string(n[t]) + "\t" + fmt(mean[t]) + "\t" +
-                fmt(sd[t]) + "\t" + fmt(r2[t]) + "\n";
+    {
+        const std::string mode = adjust[t] ? (transform[t] ? "adjusted+rint" : "adjusted") : (transform[t] ? "rint" : "standardised");
+        text += Y.names[t] + "\t" + mode + "\t" + std::to_string(n[t]) + "\t" + fmt(mean[t]) + "\t" + fmt(sd[t]) + "\t" + fmt(r2[t]);
+        if (with_rint) text += "\t" + fmt(rint_mean[t]) + "\t" + fmt(rint_sd[t]);
+        text += "\n";
+    }
     rep.put(text);
     rep.close();
     tm.mark("write files");

@@ -575,6 +575,44 @@ class Engine:
         lib().cusk_phen_timing(self.h, _ptr(ms))
         return ms
 
+    def phen_rint(self, vals, N: int, p: int, select=None, offset: float = 0.375, out=None, stats=None, ranks: bool = False):
+        """cusk_phen_rint -> dict(out p x N float32, n, mean, sd, status[, rank2 p x N uint32]): the rank-based inverse normal
+        transform of the selected traits (default all): average ranks over the finite values, normal scores of
+        (rank - offset) / (n + 1 - 2 offset), standardised to mean 0 and population sd 1; the rule is stated in
+        include/cusk_hip.h.  vals p x N float32, NaN / Inf = missing, a host array or a DeviceArray.  A trait that is not
+        selected passes through.  `out` (p * N float32 at its start) and `stats` (dict of preallocated n / mean / sd / status /
+        rank2 arrays) let a caller put guards behind the results; ranks=True also returns rank2 = twice the average rank."""
+        N, p = int(N), int(p)
+        if isinstance(vals, DeviceArray):
+            vals_p = vals.ptr
+        else:
+            vals = np.ascontiguousarray(vals, np.float32)
+            vals_p = _ptr(vals)
+        if select is not None:
+            select = np.ascontiguousarray(select, np.uint8)
+            if select.size != p:
+                raise ValueError("one select flag per trait is needed")
+        stats = dict(stats or {})
+        res = {"out": np.empty(p * N, np.float32) if out is None else out,
+               "n": stats.get("n", np.zeros(p, np.int32)), "mean": stats.get("mean", np.zeros(p)), "sd": stats.get("sd", np.zeros(p)),
+               "status": stats.get("status", np.zeros(p, np.int32))}
+        if ranks or "rank2" in stats:
+            res["rank2"] = stats.get("rank2", np.zeros(p * N, np.uint32))
+        self._check(lib().cusk_phen_rint(self.h, vals_p, N, p, _ptr(select), float(offset), _ptr(res["out"]), _ptr(res["n"]),
+                                         _ptr(res["mean"]), _ptr(res["sd"]), _ptr(res["status"]), _ptr(res.get("rank2"))))
+        res["out"] = res["out"][:p * N].reshape(p, N)
+        if "rank2" in res:
+            res["rank2"] = res["rank2"][:p * N].reshape(p, N)
+        for key in ("n", "mean", "sd", "status"):
+            res[key] = res[key][:p]
+        return res
+
+    def phen_rint_timing(self):
+        """cusk_phen_rint_timing: ms of keys, sort, ranks, moments + standardise in the last phen_rint"""
+        ms = np.zeros(4, np.float32)
+        lib().cusk_phen_rint_timing(self.h, _ptr(ms))
+        return ms
+
     def ordinal_tables(self, bed, phen, N: int, p: int, ord_ix, levels, nlev, k: int | None = None, marker_ix=None,
                        m_total: int | None = None, want_mxo: bool = True):
         """cusk_ordinal_tables -> (mxo k x q x 3 x 8, oxo q x q x 8 x 8) int32 contingency tables of the ordinal traits

@@ -134,7 +134,9 @@ const char *cusk_last_error(const cusk_engine *e);
  * cusk_sepselect_greedy for candidate lists too long for LDS, default 4 GiB; such pairs run in batches of what fits), "mvivw_part_bytes" (HBM of cusk_mvivw's chunk partials alive at
  * once, default 256 MiB; outcomes run in groups of what fits, an outcome that alone exceeds it as a group of its own; the
  * results do not depend on it), "mvivw_ld_bytes" (HBM of cusk_mvivw_ld's m x m workspace, default 8 GiB; an outcome that
- * needs more is an argument error). */
+ * needs more is an argument error), "phen_rint_bytes" (HBM of cusk_phen_rint's sorted keys and ranks alive at once, default
+ * 1 GiB; traits run in groups of what fits, the results do not depend on it, and a single trait that needs more is an
+ * argument error). */
 int cusk_engine_set_option(cusk_engine *e, const char *key, long long value);
 /* Host only, no device needed: the workgroup size level 1's row-streaming kernel runs with when a row of C takes
  * row_bytes of LDS (4 (n + 8) for a single n x n matrix), or 0 when it gathers the row through the caches instead.
@@ -574,6 +576,41 @@ int cusk_phen_moments(cusk_engine *e, const float *phen, size_t N, size_t p, int
 /* HIP-event times of the last cusk_phen_adjust on e: covariate mask and scaling, Gram partials, their ordered sum and the
  * Cholesky solves, residual moments (both passes), standardise.  ms5: 5 floats. */
 void cusk_phen_timing(cusk_engine *e, float *ms5);
+
+/* `prep-phen ... rint`: the rank-based inverse normal transform of traits, on the device (phen_rint.hip).  Every test
+ * downstream is a Fisher-z test on Pearson correlations of the traits; a skewed trait or one with a few extreme values
+ * biases them, and standardising does not repair that.  vals p x N float32 trait-major, host memory or device-resident as
+ * cusk_phen_adjust takes phen; NaN or +-Inf = missing.  For a trait t with select[t] != 0 (select == NULL: every trait):
+ *   1. U = { i : vals[t, i] finite }, n = |U|
+ *   2. values are ordered as floats, -0.0 equal to +0.0: the key of a value is the usual order-preserving uint32 image of
+ *      its bits (sign bit set for a non-negative value, all bits flipped for a negative one) with -0.0 on the image of
+ *      +0.0; a missing value has the key 0xFFFFFFFF, which no finite float has, so missing values sort last
+ *   3. lo_i = #{ j in U : v_j < v_i }, eq_i = #{ j in U : v_j = v_i }; the average rank r_i = lo_i + (eq_i + 1) / 2 is
+ *      carried as the integer rank2_i = 2 lo_i + eq_i + 1 <= 2 N, which fits 32 bits because N < 2^31
+ *   4. q_i = ppnd16((r_i - offset) / ((n + 1) - 2 offset)) in IEEE double: Wichura's AS 241 as csrc/ordinal_math.h has it,
+ *      without a Newton step; 0 <= offset <= 0.5, 0.375 is Blom's
+ *   5. m = sum(q) / n, s = sqrt(sum((q - m)^2) / n), two passes, summed as step 7 of cusk_phen_adjust sums: over chunks of
+ *      CUSK_PHEN_CHUNK individuals in a fixed order, the partials added in chunk order, no floating-point atomics;
+ *      out[t, i] = (float)((q_i - m) / s) for i in U, NaN elsewhere
+ *   6. status[t]: CUSK_PHEN_OK, or CUSK_PHEN_TOO_FEW when n < 2 or s == 0 (every value equal: every score is then
+ *      ppnd16(1/2) = 0); then the row of out is all NaN and mean / sd are NaN
+ * A trait that is not selected: its row of out_host receives the input row's bytes, n = its count of finite values, mean /
+ * sd NaN, status OK, rank2 0.
+ * Consequences: equal inputs give bitwise-equal outputs (q is a function of the integer rank2 and n alone); the output is
+ * non-decreasing in the input; two calls give the same bytes; nothing depends on how traits are grouped.
+ * Outputs (HOST; out_host p x N; n / mean / sd / status per trait; rank2_out p x N: rank2_i, 0 for a missing value; any of
+ * n / mean / sd / status / rank2 may be NULL).  Workspace: 4 (Npad + N) bytes per selected trait, Npad = the next power of
+ * two >= max(N, cusk_phen_rint_tile()), from the engine's scratch; traits run in groups that keep it within engine option
+ * "phen_rint_bytes".  CUSK_ERR_ARG (message in cusk_last_error, nothing launched, no output written): a null engine, vals
+ * or out_host, N == 0, p == 0, N >= 2^31, an offset outside [0, 0.5] or NaN, a selected trait whose workspace alone
+ * exceeds "phen_rint_bytes". */
+int cusk_phen_rint(cusk_engine *e, const float *vals, size_t N, size_t p, const unsigned char *select, double offset,
+                   float *out_host, int *n_out, double *mean_out, double *sd_out, int *status_out, unsigned *rank2_out);
+/* HIP-event times of the last cusk_phen_rint on e, summed over its groups: keys, sort, ranks, moments + standardise.
+ * ms4: 4 floats. */
+void cusk_phen_rint_timing(cusk_engine *e, float *ms4);
+/* Host only: the keys one workgroup sorts in LDS (a power of two). */
+size_t cusk_phen_rint_tile(void);
 
 /* Host only.  A trait or covariate table read and aligned to a .fam (host/phen_table.h).  Whitespace-separated text; the
  * header names two id columns, FID and IID in either order (IID may be called EID), then the value columns; NA tokens are
