@@ -278,7 +278,8 @@ def _add_mvivw(sub):
     """ci-gwas.py:272-301, with the selections of both of the reference's R scripts and the choices the R back-end fixes"""
     p = sub.add_parser("mvivw", help="Multivariable inverse-variance weighted Mendelian randomisation between the traits, "
                                      "using cusk-identified markers as instrumental variables: the plain IVW estimator with "
-                                     "multiplicative random effects, not the reference's robust one (requires GPU)")
+                                     "multiplicative random effects, or with --robust a stated M-estimator; neither is the "
+                                     "reference's lmrob (requires GPU)")
     p.add_argument("cusk_output_stem", metavar="cusk-output-stem", type=str, help="output stem of cusk or cuskss result files")
     p.add_argument("num_samples", metavar="num-samples", type=TypeCheck(int, "num-samples", 1, None),
                    help="number of samples used for computing correlations")
@@ -301,6 +302,12 @@ def _add_mvivw(sub):
                         "<cusk-output-stem>_scm.mtx as their LD; <stem>_mvivw_outcomes.tsv gains the column ld_pivot")
     p.add_argument("--ld-ridge", metavar="L", type=TypeCheck(float, "ld-ridge", 0.0, None), default=None,
                    help="with --ld: shrink the LD towards the identity, (1 - L) R + L I, 0 <= L < 1 (default 0)")
+    p.add_argument("--robust", nargs="?", const="bisquare", default=None, choices=("huber", "bisquare"),
+                   help="outlier-resistant estimates by iteratively reweighted least squares: huber, or bisquare (Huber, "
+                        "then Tukey bisquare weights; the default of a bare --robust).  A stated, deterministic M-estimator, "
+                        "not the reference's lmrob.  <stem>_mvivw_outcomes.tsv gains the columns scale tau iterations rho_sum")
+    p.add_argument("--robust-weights", metavar="FILE", type=str, default=None,
+                   help="with --robust: write sink, marker, rho of every instrument whose final weight rho is below 1")
     p.add_argument("--out", type=str, default=None, help="output file (default <cusk-output-stem>_mvivw_results.tsv)")
     p.set_defaults(func=run_mvivw, parser=p)
 
@@ -609,14 +616,22 @@ def run_mvivw(args):
         args.parser.error("--ld-ridge needs --ld")
     if args.ld_ridge is not None and not args.ld_ridge < 1.0:
         args.parser.error("--ld-ridge must be in [0, 1)")
+    if args.robust and args.ld:
+        args.parser.error("--robust cannot be combined with --ld: whitening mixes the rows, so a weight per instrument "
+                          "has no meaning there")
+    if args.robust_weights and not args.robust:
+        args.parser.error("--robust-weights needs --robust")
     data = load(stem, het=args.het)  # unreadable inputs are reported before an engine exists; read once
     write_csv(f"{stem}_iv_candidates.csv", iv_candidates(stem, data=data))
     mode = "skeleton" if args.s else "prior" if args.orientation_prior else "ivs" if args.ivs else "all"
     res = mvivw.run(stem, args.num_samples, mode=mode, prior_path=args.orientation_prior, ivs_path=args.ivs, het=args.het,
-                    model=mvivw.MODELS[args.model], engine=_mvivw_engine(), data=data, ld=args.ld, ld_ridge=args.ld_ridge or 0.0)
+                    model=mvivw.MODELS[args.model], engine=_mvivw_engine(), data=data, ld=args.ld, ld_ridge=args.ld_ridge or 0.0,
+                    robust=args.robust)
     out = args.out or f"{stem}_mvivw_results.tsv"
     mvivw.write_results(out, res)
     mvivw.write_outcomes(f"{out[:-len('_results.tsv')]}_outcomes.tsv" if out.endswith("_results.tsv") else f"{out}.outcomes.tsv", res)
+    if args.robust_weights:
+        mvivw.write_weights(args.robust_weights, res)
     print(f"mvivw: {int((res['status'] == 0).sum())} of {res['p']} outcomes estimated.")
 
 

@@ -10,7 +10,8 @@
 //                     W Z stands in LDS; thread t owns a TS x TS tile of the lower triangle of Z'WZ (TS = 2, 4, 8 by the
 //                     number of columns, so that the tiles of the widest problem of a class fill the workgroup) in
 //                     double registers and walks the slab with plain FMAs on the FP64 vector pipe.  The staging pass
-//                     also notes a NaN, an infinity or a weight <= 0 among the chunk's values (status 3).
+//                     also notes a NaN, an infinity or a weight <= 0 among the chunk's values (status 3).  Its RHO form
+//                     (mvivw_robust.hip) multiplies every weight by a per-row rho.
 //   mv_solve_kernel   one workgroup per outcome: the ordered sum of the partials, the Gram scaled to unit diagonal as a
 //                     packed triangle in LDS, right-looking Cholesky with the pivot test, both substitutions, the inverse
 //                     of the factor in place and from it diag(G^-1).
@@ -30,7 +31,9 @@ namespace cusk {
 
 namespace {
 
-template <int TS, int LD, int SLAB>
+// RHO: the form of mvivw_robust.hip.  The weight of list position i is w_i b.rho[i], the chunks of a frozen outcome are
+// left alone, and the values are not tested again (the plain pass of the same call has set the flags).
+template <int TS, int LD, int SLAB, bool RHO>
 __global__ void __launch_bounds__(256) mv_gram_kernel(MvBatch b, const MvChunk *__restrict__ chunks)
 {
     __shared__ double zs[SLAB * LD];
@@ -38,6 +41,8 @@ __global__ void __launch_bounds__(256) mv_gram_kernel(MvBatch b, const MvChunk *
     __shared__ int cols[LD];
     const int tid = threadIdx.x;
     const MvChunk ch = chunks[blockIdx.x];
+    if constexpr (RHO)
+        if (b.frozen[ch.slot]) return;  // the same for the whole workgroup
     const MvOutcome q = b.outs[ch.slot];
     const int k = q.k, K = k + 1, p = b.p;
     const int T = (K + TS - 1) / TS, ntiles = T * (T + 1) / 2;  // T * TS <= LD by the class table
@@ -50,6 +55,7 @@ __global__ void __launch_bounds__(256) mv_gram_kernel(MvBatch b, const MvChunk *
         for (int j = 0; j < TS; j++) acc[i][j] = 0.0;
     const int rows = min(kMvChunk, q.m - ch.chunk * kMvChunk);
     const int *ivp = b.iv + q.iv0 + (long long)ch.chunk * kMvChunk;
+    [[maybe_unused]] const double *rhop = RHO ? b.rho + q.iv0 + (long long)ch.chunk * kMvChunk : nullptr;
     int bad = 0;
     __syncthreads();
     for (int s0 = 0; s0 < rows; s0 += SLAB)
@@ -61,7 +67,8 @@ __global__ void __launch_bounds__(256) mv_gram_kernel(MvBatch b, const MvChunk *
             if (s0 + r < rows && c < K)
             {
                 const size_t base = (size_t)ivp[s0 + r] * p;
-                const double w = b.weight[base + q.o];
+                double w = b.weight[base + q.o];
+                if constexpr (RHO) w = w * rhop[s0 + r];
                 x = b.beta[base + cols[c]];
                 wx = w * x;
                 bad |= (!mv_finite(x)) | (!(w > 0.0 && w <= DBL_MAX));
@@ -73,8 +80,11 @@ __global__ void __launch_bounds__(256) mv_gram_kernel(MvBatch b, const MvChunk *
         if (tid < ntiles) mv_slab_walk<TS, LD, SLAB>(ws + ti * TS, zs + tj * TS, acc);
         __syncthreads();
     }
-    bad = __syncthreads_or(bad);
-    if (tid == 0) b.chunk_bad[q.chunk0 + ch.chunk] = bad ? 1 : 0;
+    if constexpr (!RHO)
+    {
+        bad = __syncthreads_or(bad);
+        if (tid == 0) b.chunk_bad[q.chunk0 + ch.chunk] = bad ? 1 : 0;
+    }
     if (tid < ntiles) mv_store_tile<TS>(b.part + q.part0 + (long long)ch.chunk * (K * (K + 1) / 2), K, ti, tj, acc);
 }
 
@@ -82,6 +92,7 @@ __global__ void __launch_bounds__(256) mv_solve_kernel(MvBatch b, int first)
 {
     extern __shared__ double s_mem[];
     const int tid = threadIdx.x, slot = first + blockIdx.x;
+    if (b.frozen && b.frozen[slot]) return;  // mvivw_robust.hip: the outcome keeps its last solution
     const MvOutcome q = b.outs[slot];
     const int k = q.k, K = k + 1, E = K * (K + 1) / 2, EL = k * (k + 1) / 2;
     double *L = s_mem;
@@ -128,6 +139,7 @@ __global__ void __launch_bounds__(256) mv_solve_kernel(MvBatch b, int first)
         }
         return;
     }
+    if (b.dsc && tid < k) b.dsc[(size_t)slot * kMvVec + tid] = d[tid];
     if (tid < k)
     {
         const int rr = tid * (tid + 1) / 2;
@@ -304,6 +316,27 @@ void launch_mv_finish(hipStream_t s, const MvBatch &b, int first, unsigned nslot
 }
 
 namespace {
+template <bool RHO>
+void launch_mv_gram_form(hipStream_t s, const MvBatch &b, int cls, const MvChunk *chunks, size_t cnt)
+{
+    if (cls == 0)
+        hipLaunchKernelGGL((mv_gram_kernel<2, 44, 32, RHO>), dim3((unsigned)cnt), dim3(256), 0, s, b, chunks);
+    else if (cls == 1)
+        hipLaunchKernelGGL((mv_gram_kernel<4, 88, 32, RHO>), dim3((unsigned)cnt), dim3(256), 0, s, b, chunks);
+    else
+        hipLaunchKernelGGL((mv_gram_kernel<8, 128, 16, RHO>), dim3((unsigned)cnt), dim3(256), 0, s, b, chunks);
+}
+}  // namespace
+
+void launch_mv_gram(hipStream_t s, const MvBatch &b, int cls, const MvChunk *chunks, size_t cnt, bool with_rho)
+{
+    if (with_rho)
+        launch_mv_gram_form<true>(s, b, cls, chunks, cnt);
+    else
+        launch_mv_gram_form<false>(s, b, cls, chunks, cnt);
+}
+
+namespace {
 
 int mvivw_impl(cusk_engine *e, const double *beta, const double *weight, long long M, int p, int nout, const int *outcome,
                const long long *iv_off, const int *iv, const int *ex_off, const int *ex, int model, double *theta, double *se,
@@ -358,13 +391,7 @@ int mvivw_impl(cusk_engine *e, const double *beta, const double *weight, long lo
             {
                 const size_t cnt = g.class_first[c + 1] - g.class_first[c];
                 if (cnt == 0) continue;
-                const MvChunk *cl = chunks + g.class_first[c];
-                if (c == 0)
-                    hipLaunchKernelGGL((mv_gram_kernel<2, 44, 32>), dim3((unsigned)cnt), dim3(256), 0, s, b, cl);
-                else if (c == 1)
-                    hipLaunchKernelGGL((mv_gram_kernel<4, 88, 32>), dim3((unsigned)cnt), dim3(256), 0, s, b, cl);
-                else
-                    hipLaunchKernelGGL((mv_gram_kernel<8, 128, 16>), dim3((unsigned)cnt), dim3(256), 0, s, b, cl);
+                launch_mv_gram(s, b, c, chunks + g.class_first[c], cnt, false);
                 CUSK_HIP(e, hipGetLastError());
             }
             const unsigned nslots = (unsigned)(g.last - g.first);

@@ -41,6 +41,10 @@ struct MvBatch
     double *theta;    // layout of ex
     double *se;       // layout of ex
     double *stats;    // per active outcome: rss, sigma, smallest squared pivot
+    // mvivw_robust.hip alone sets what follows; null: the plain regressions
+    const double *rho = nullptr;  // layout of iv: the Gram kernel multiplies the weight of a list position by it
+    const int *frozen = nullptr;  // per active outcome: not 0 = the Gram (rho form) and solve kernels leave it as it is
+    double *dsc = nullptr;        // per active outcome: kMvVec doubles, the solve kernel's d_j = sqrt(G_jj)
 };
 
 __device__ __forceinline__ bool mv_finite(double v) { return fabs(v) <= DBL_MAX; }  // false for NaN
@@ -105,23 +109,26 @@ __device__ __forceinline__ double mv_block_sum(double term, double *sh)
 hipError_t mv_reg_prepare();  // once per call, before the first launch: the dynamic LDS of the solve kernel
 void launch_mv_solve(hipStream_t s, const MvBatch &b, int first, unsigned nslots);
 void launch_mv_finish(hipStream_t s, const MvBatch &b, int first, unsigned nslots);
+// mv_gram_kernel of tile class `cls` for `cnt` chunks; with_rho: the form that multiplies every weight by b.rho and
+// skips the chunks of frozen outcomes (mvivw_robust.hip)
+void launch_mv_gram(hipStream_t s, const MvBatch &b, int cls, const MvChunk *chunks, size_t cnt, bool with_rho);
 
 // What the two entry points keep per call beside their tables: the device arrays the solve and finish kernels write,
 // per active outcome (na) and per exposure position (nex), and their host copies.
 struct MvResults
 {
-    size_t na, nex;
+    size_t na, nex, ncol;  // ncol: columns of stats
     ScopedDevBuf d_sol, d_status, d_theta, d_se, d_stats;
     std::vector<double> theta, se, stats;
     std::vector<int> status;
-    MvResults(size_t na_, size_t nex_)
-        : na(na_), nex(nex_), theta(nex_, kMvNaN), se(nex_, kMvNaN), stats(na_ * 3, kMvNaN), status(na_, 0)
+    MvResults(size_t na_, size_t nex_, size_t ncol_ = 3)
+        : na(na_), nex(nex_), ncol(ncol_), theta(nex_, kMvNaN), se(nex_, kMvNaN), stats(na_ * ncol_, kMvNaN), status(na_, 0)
     {
     }
     hipError_t alloc(MvBatch &b)
     {
         const size_t bytes[5] = {sizeof(double) * na * kMvSolLd, sizeof(int) * na, sizeof(double) * (nex > 0 ? nex : 1),
-                                 sizeof(double) * (nex > 0 ? nex : 1), sizeof(double) * na * 3};
+                                 sizeof(double) * (nex > 0 ? nex : 1), sizeof(double) * na * ncol};
         DevBuf *const bufs[5] = {&d_sol, &d_status, &d_theta, &d_se, &d_stats};
         for (int i = 0; i < 5; i++)
         {
@@ -140,7 +147,7 @@ struct MvResults
         hipError_t st = hipSuccess;
         if (nex) st = hipMemcpyAsync(theta.data(), d_theta.p, sizeof(double) * nex, hipMemcpyDeviceToHost, s);
         if (nex && st == hipSuccess) st = hipMemcpyAsync(se.data(), d_se.p, sizeof(double) * nex, hipMemcpyDeviceToHost, s);
-        if (st == hipSuccess) st = hipMemcpyAsync(stats.data(), d_stats.p, sizeof(double) * na * 3, hipMemcpyDeviceToHost, s);
+        if (st == hipSuccess) st = hipMemcpyAsync(stats.data(), d_stats.p, sizeof(double) * na * ncol, hipMemcpyDeviceToHost, s);
         if (st == hipSuccess) st = hipMemcpyAsync(status.data(), d_status.p, sizeof(int) * na, hipMemcpyDeviceToHost, s);
         return st;
     }
@@ -149,12 +156,12 @@ struct MvResults
 // the caller's arrays before any result goes in: the plan's status (1 where nothing is computed), NaN everywhere else.
 // Nothing of the caller's is written before this.
 inline void mv_fill_unset(int nout, const std::vector<int> &plan_status, const int *ex_off, double *theta, double *se, double *stats,
-                          int *status)
+                          int *status, int ncol = 3)
 {
     for (int a = 0; a < nout; a++)
     {
         status[a] = plan_status[(size_t)a];
-        for (int c = 0; c < 3; c++) stats[(size_t)a * 3 + c] = kMvNaN;
+        for (int c = 0; c < ncol; c++) stats[(size_t)a * ncol + c] = kMvNaN;
         for (int c = ex_off[a]; c < ex_off[a + 1]; c++) theta[c] = se[c] = kMvNaN;
     }
 }

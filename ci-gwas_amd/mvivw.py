@@ -135,25 +135,20 @@ def check_arguments(M, p, outcome, iv_off, iv, ex_off, ex, model):
             raise ValueError(f"mvivw: outcome {a}: the exposure list is not strictly ascending inside [0, p) without the outcome")
 
 
-def solve_one(X, y, w, model: int):
-    """One problem by the rule of include/cusk_hip.h -> (status, theta, se, (rss, sigma, smallest squared pivot))"""
+def _gram_solve(Z, w):
+    """Steps 1 - 3 of the rule for Z = (X, y) with the row weights w -> (status 0 | 2, theta, v, d, pivot): the smallest
+    squared pivot, or the one that failed (0 for a G_jj that is not positive)"""
     from scipy.linalg import solve_triangular
 
-    m, k = X.shape
-    nan3 = (np.nan, np.nan, np.nan)
-    if k == 0 or m <= k:
-        return 1, None, None, nan3
-    if not (np.isfinite(X).all() and np.isfinite(y).all() and np.isfinite(w).all() and (w > 0).all()):
-        return 3, None, None, nan3
-    Z = np.concatenate([X, y[:, None]], axis=1)
-    S = np.zeros((k + 1, k + 1))
+    m, k = Z.shape[0], Z.shape[1] - 1
+    S = np.zeros((k + 1, k + 1), Z.dtype)
     for c0 in range(0, m, CHUNK):  # chunk partials, added in chunk order
         Zc = Z[c0:c0 + CHUNK]
         S += (Zc * w[c0:c0 + CHUNK, None]).T @ Zc
     G, b = S[:k, :k], S[k, :k]
     dg = np.diag(G)
     if not (dg > 0).all():
-        return 2, None, None, (np.nan, np.nan, 0.0)
+        return 2, None, None, None, 0.0
     d = np.sqrt(dg)
     L = np.tril(G / np.outer(d, d))
     np.fill_diagonal(L, 1.0)
@@ -162,13 +157,34 @@ def solve_one(X, y, w, model: int):
         piv = L[j, j]
         minpiv = min(minpiv, piv)
         if not piv >= PIVOT_MIN:
-            return 2, None, None, (np.nan, np.nan, float(piv))
+            return 2, None, None, None, float(piv)
         L[j, j] = np.sqrt(piv)
         L[j + 1:, j] /= L[j, j]
         L[j + 1:, j + 1:] -= np.tril(np.outer(L[j + 1:, j], L[j + 1:, j]))
-    Linv = solve_triangular(L, np.eye(k), lower=True)
+    if Z.dtype == np.float64:
+        Linv = solve_triangular(L, np.eye(k), lower=True)
+    else:  # the extended-precision restatement of the tests: scipy has no such solver
+        Linv = np.zeros((k, k), Z.dtype)
+        for j in range(k):
+            Linv[j, j] = 1 / L[j, j]
+            for i in range(j + 1, k):
+                Linv[i, j] = -(L[i, j:i] @ Linv[j:i, j]) / L[i, i]
     theta = (Linv.T @ (Linv @ (b / d))) / d
     v = (Linv * Linv).sum(axis=0) / (d * d)
+    return 0, theta, v, d, float(minpiv)
+
+
+def solve_one(X, y, w, model: int):
+    """One problem by the rule of include/cusk_hip.h -> (status, theta, se, (rss, sigma, smallest squared pivot))"""
+    m, k = X.shape
+    nan3 = (np.nan, np.nan, np.nan)
+    if k == 0 or m <= k:
+        return 1, None, None, nan3
+    if not (np.isfinite(X).all() and np.isfinite(y).all() and np.isfinite(w).all() and (w > 0).all()):
+        return 3, None, None, nan3
+    st, theta, v, _, minpiv = _gram_solve(np.concatenate([X, y[:, None]], axis=1), w)
+    if st != 0:
+        return st, None, None, (np.nan, np.nan, minpiv)
     r = y - X @ theta
     t = w * (r * r)
     rss = 0.0
@@ -178,6 +194,96 @@ def solve_one(X, y, w, model: int):
     random = model == 1 or (model == 0 and m >= 4)
     se = np.sqrt(v) * (sigma if random and sigma > 1.0 else 1.0)
     return 0, theta, se, (rss, sigma, float(minpiv))
+
+
+PSI = {"huber": 1, "bisquare": 2}
+MAX_UPDATES = 100                  # per stage
+MAD, HUBER_C, BISQUARE_C, ROBUST_TOL = 1.4826, 1.345, 4.685, 1e-10
+
+
+def abs_median(e):
+    """The exact median of |e|: the middle value of the sorted absolute values, or (a + b) * 0.5 of the two middle ones"""
+    a = np.sort(np.abs(e))
+    n = a.shape[0]
+    return a[n // 2] if n & 1 else (a[n // 2 - 1] + a[n // 2]) * 0.5
+
+
+def robust_rho(e, s, stage: int):
+    """(rho, psi') of the residuals e at the scale s: stage 0 Huber, 1 bisquare"""
+    one, zero = e.dtype.type(1), e.dtype.type(0)
+    if stage == 0:
+        a, c = np.abs(e), e.dtype.type(HUBER_C) * s
+        inside = a <= c
+        with np.errstate(all="ignore"):
+            return np.where(inside, one, c / a), np.where(inside, one, zero)
+    u = e / (e.dtype.type(BISQUARE_C) * s)
+    u2 = u * u
+    inside = np.abs(u) < 1
+    return np.where(inside, (1 - u2) * (1 - u2), zero), np.where(inside, (1 - u2) * (1 - 5 * u2), zero)
+
+
+def _chunk_sum(t):
+    tot = t.dtype.type(0)
+    for c0 in range(0, t.shape[0], CHUNK):
+        tot += t[c0:c0 + CHUNK].sum()
+    return tot
+
+
+def solve_one_robust(X, y, w, model: int, psi: int, max_updates: int = MAX_UPDATES):
+    """One problem of `cusk_mvivw_robust` by the rule of include/cusk_hip.h, in the floating-point type of X (float64; the
+    tests restate it in np.longdouble by passing such arrays).  `max_updates`: the cap per stage, 100 in the rule.
+    -> (status, theta, se, (rss, s, tau, smallest squared pivot of the last weighted Gram, updates, sum rho), rho)"""
+    m, k = X.shape
+    ft = X.dtype.type
+    nan6 = (np.nan,) * 6
+    if psi not in (1, 2):
+        raise ValueError(f"mvivw: psi {psi} is not 1 (Huber) or 2 (bisquare)")
+    if k == 0 or m <= k:
+        return 1, None, None, nan6, None
+    if not (np.isfinite(X).all() and np.isfinite(y).all() and np.isfinite(w).all() and (w > 0).all()):
+        return 3, None, None, nan6, None
+    Z = np.concatenate([X, y[:, None]], axis=1)
+    sw = np.sqrt(w)
+
+    def failed(st, piv=np.nan):
+        return st, None, None, (np.nan, np.nan, np.nan, piv, np.nan, np.nan), None
+
+    st, theta, v, d, piv = _gram_solve(Z, w)
+    if st != 0:
+        return failed(st, piv)
+    e = sw * (y - X @ theta)
+    s = ft(MAD) * abs_median(e)
+    if not s > 0:
+        return failed(6)
+    updates = 0
+    for stage in range(psi):
+        for t in range(max_updates):
+            rho, _ = robust_rho(e, s, stage)
+            st, new, _, _, piv = _gram_solve(Z, w * rho)
+            if st != 0:
+                return failed(st, piv)
+            e = sw * (y - X @ new)
+            if stage == 0:
+                s = ft(MAD) * abs_median(e)
+                if not s > 0:
+                    return failed(6)
+            updates += 1
+            step = np.max(d * np.abs(new - theta))
+            theta = new
+            if step <= ft(ROBUST_TOL) * s * np.sqrt(ft(m)):
+                break
+        else:
+            return failed(5)
+    rho, dpsi = robust_rho(e, s, psi - 1)
+    ps = e * rho
+    A, B = _chunk_sum(ps * ps) / ft(m - k), _chunk_sum(dpsi) / ft(m)
+    if not B > 0:
+        return failed(5)
+    tau = np.sqrt(A) / B
+    random = model == 1 or (model == 0 and m >= 4)
+    g = tau if random else tau / s
+    se = np.sqrt(v) * (g if g > 1 else ft(1))
+    return 0, theta, se, (_chunk_sum(e * e), s, tau, piv, updates, _chunk_sum(rho)), rho
 
 
 LD_PANEL = 64  # kLdPanel of csrc/host/mvivw_ld_plan.h
@@ -233,8 +339,8 @@ class HostEngine:
     the tests"""
 
     @staticmethod
-    def _run(beta, weight, outcome, iv_off, iv, ex_off, ex, model, solve):
-        """The batch both methods walk; `solve(I, E, o)` -> (status, theta, se, stats) of one outcome (solve_one's)"""
+    def _run(beta, weight, outcome, iv_off, iv, ex_off, ex, model, solve, ncol=3, dtype=np.float64):
+        """The batch every method walks; `solve(I, E, o, a)` -> (status, theta, se, stats) of outcome a (solve_one's)"""
         M, p = beta.shape
         outcome = np.asarray(outcome, np.int64).reshape(-1)
         iv_off, ex_off = np.asarray(iv_off, np.int64).reshape(-1), np.asarray(ex_off, np.int64).reshape(-1)
@@ -242,10 +348,10 @@ class HostEngine:
         check_arguments(M, p, outcome, iv_off, iv, ex_off, ex, model)
         nout = outcome.shape[0]
         nex = int(ex_off.max()) if nout else 0
-        theta, se = np.full(max(nex, 1), np.nan), np.full(max(nex, 1), np.nan)
-        stats, status = np.full((nout, 3), np.nan), np.zeros(nout, np.int32)
+        theta, se = np.full(max(nex, 1), np.nan, dtype), np.full(max(nex, 1), np.nan, dtype)
+        stats, status = np.full((nout, ncol), np.nan, dtype), np.zeros(nout, np.int32)
         for a, o in enumerate(outcome):
-            st, th, s, stat = solve(iv[iv_off[a]:iv_off[a + 1]], ex[ex_off[a]:ex_off[a + 1]], o)
+            st, th, s, stat = solve(iv[iv_off[a]:iv_off[a + 1]], ex[ex_off[a]:ex_off[a + 1]], o, a)
             status[a], stats[a] = st, stat
             if st == 0:
                 theta[ex_off[a]:ex_off[a + 1]] = th
@@ -259,22 +365,47 @@ class HostEngine:
             raise ValueError(f"mvivw: ld is not {M} x {M}")
         if not 0.0 <= ridge < 1.0:
             raise ValueError("mvivw: ridge is not in [0, 1)")
-        return self._run(beta, weight, outcome, iv_off, iv, ex_off, ex, model, lambda I, E, o: solve_one_ld(
+        return self._run(beta, weight, outcome, iv_off, iv, ex_off, ex, model, lambda I, E, o, a: solve_one_ld(
             beta[np.ix_(I, E)], beta[I, o], weight[I, o], ld[np.ix_(I, I)], model, ridge))
 
     def mvivw(self, beta, weight, outcome, iv_off, iv, ex_off, ex, model=0):
         beta, weight = np.asarray(beta, np.float64), np.asarray(weight, np.float64)
-        return self._run(beta, weight, outcome, iv_off, iv, ex_off, ex, model, lambda I, E, o: solve_one(
+        return self._run(beta, weight, outcome, iv_off, iv, ex_off, ex, model, lambda I, E, o, a: solve_one(
             beta[np.ix_(I, E)], beta[I, o], weight[I, o], model))
+
+    def mvivw_robust(self, beta, weight, outcome, iv_off, iv, ex_off, ex, model=0, psi=2, want_rho=True, dtype=np.float64,
+                     max_updates=MAX_UPDATES):
+        """`Engine.mvivw_robust`; `dtype` np.longdouble gives the extended-precision restatement of the tests"""
+        beta, weight = np.asarray(beta, dtype), np.asarray(weight, dtype)
+        if psi not in (1, 2):
+            raise ValueError(f"mvivw: psi {psi} is not 1 (Huber) or 2 (bisquare)")
+        iv_off = np.asarray(iv_off, np.int64).reshape(-1)
+        rho = np.full(max(int(iv_off.max()) if len(iv_off) else 0, 1), np.nan, dtype)
+
+        def solve(I, E, o, a):
+            st, th, se, stat, r = solve_one_robust(beta[np.ix_(I, E)], beta[I, o], weight[I, o], model, psi, max_updates)
+            if st == 0:
+                rho[iv_off[a]:iv_off[a + 1]] = r
+            return st, th, se, stat
+
+        theta, se, stats, status, ms = self._run(beta, weight, outcome, iv_off, iv, ex_off, ex, model, solve, ncol=6, dtype=dtype)
+        return theta, se, stats, status, (rho if want_rho else None), ms
 
 
 def run(stem: str, num_samples: int, mode: str = "all", prior_path: str | None = None, ivs_path: str | None = None,
-        het: bool = False, model: int = 0, engine=None, data=None, ld: bool = False, ld_ridge: float = 0.0):
+        het: bool = False, model: int = 0, engine=None, data=None, ld: bool = False, ld_ridge: float = 0.0,
+        robust: str | None = None):
     """The estimates of every outcome of a merged skeleton.  `engine`: a device Engine (skeleton.Engine), or None for the
     numpy form.  `data`: what `ivcheck.load(stem, het)` returned.  Returns a dict: p, selection [(I, E)], theta, se (lists
     per outcome, None unless status 0), stats, status, sk_adj (p x p bool), kernel_ms, ld.  `ld`: the instruments are taken as
     correlated with the marker block corr[p:, p:] of the skeleton as their LD (`mvivw_ld`, ridge `ld_ridge`); stats[:, 2] is
-    then the pivot of the LD matrix and status may be 4."""
+    then the pivot of the LD matrix and status may be 4.  `robust`: None, "huber" or "bisquare" (`mvivw_robust`): stats is
+    then nout x 6 (rss, scale, tau, pivot, updates, sum of rho), status may be 5 or 6, and the dict has robust (the name) and
+    rho (per outcome the final rho of its instruments in the order of I, None unless status 0)."""
+    if robust is not None and robust not in PSI:
+        raise ValueError(f"mvivw: robust {robust!r} is not huber or bisquare")
+    if robust is not None and ld:
+        raise ValueError("mvivw: robust with ld: whitening mixes the rows, a weight per instrument has no meaning there")
     adj, corr, p, ssz = ivcheck.load(stem, het=het) if data is None else data
     beta = np.ascontiguousarray(corr[p:, :p])
     weight = weights(beta, ssz[p:, :p] if het else num_samples)
@@ -291,10 +422,15 @@ def run(stem: str, num_samples: int, mode: str = "all", prior_path: str | None =
     if ld:
         theta, se, stats, status, ms = eng.mvivw_ld(beta, weight, np.ascontiguousarray(corr[p:, p:], dtype=np.float64),
                                                     np.arange(p, dtype=np.int32), iv_off, iv, ex_off, ex, model, ridge=ld_ridge)
+    elif robust is not None:
+        theta, se, stats, status, rho, ms = eng.mvivw_robust(beta, weight, np.arange(p, dtype=np.int32), iv_off, iv, ex_off, ex,
+                                                             model, psi=PSI[robust])
     else:
         theta, se, stats, status, ms = eng.mvivw(beta, weight, np.arange(p, dtype=np.int32), iv_off, iv, ex_off, ex, model)
     ok = [int(status[o]) == 0 for o in range(p)]
-    return {"p": p, "selection": selection, "status": np.asarray(status[:p]).copy(), "stats": np.asarray(stats[:p]).copy(),
+    extra = {} if robust is None else {
+        "robust": robust, "rho": [np.array(rho[iv_off[o]:iv_off[o + 1]]) if ok[o] else None for o in range(p)]}
+    return {**extra, "p": p, "selection": selection, "status": np.asarray(status[:p]).copy(), "stats": np.asarray(stats[:p]).copy(),
             "theta": [np.array(theta[ex_off[o]:ex_off[o + 1]]) if ok[o] else None for o in range(p)],
             "se": [np.array(se[ex_off[o]:ex_off[o + 1]]) if ok[o] else None for o in range(p)],
             "sk_adj": np.asarray(adj)[:p, :p] != 0, "kernel_ms": ms, "ld": bool(ld)}
@@ -315,7 +451,7 @@ def write_results(path: str, res) -> None:
             I, E = res["selection"][o]
             st = int(res["status"][o])
             pos = {int(t): j for j, t in enumerate(E)}
-            if st in (2, 3):
+            if st in (2, 3, 5, 6):
                 print(f"mvivw: outcome trait {o + 1} (1-based): status {st}, no estimates", file=sys.stderr)
             elif st == 4:
                 print(f"mvivw: outcome trait {o + 1} (1-based): status 4, the LD matrix of its instruments is not positive "
@@ -337,20 +473,45 @@ def write_results(path: str, res) -> None:
 
 def write_outcomes(path: str, res) -> None:
     """`<stem>_mvivw_outcomes.tsv`: per outcome the heterogeneity statistic q = rss and its upper chi-square tail; with
-    `--ld` a last column ld_pivot, the smallest squared pivot of the LD matrix (status 4: the pivot that failed)"""
+    `--ld` a last column ld_pivot, the smallest squared pivot of the LD matrix (status 4: the pivot that failed); with
+    `--robust` the last columns scale, tau, iterations, rho_sum of the robust fit, q = the plain rss at the robust estimate
+    and sigma = sqrt(q / (m - k))"""
     from scipy.stats import chi2
 
-    with_ld = bool(res.get("ld"))
+    with_ld, robust = bool(res.get("ld")), res.get("robust") is not None
     with open(path, "w") as f:
-        f.write("sink\tn_exposures\tnum_snps\tsigma\tq\tq_p\tstatus" + ("\tld_pivot" if with_ld else "") + "\n")
+        f.write("sink\tn_exposures\tnum_snps\tsigma\tq\tq_p\tstatus" + ("\tld_pivot" if with_ld else "")
+                + ("\tscale\ttau\titerations\trho_sum" if robust else "") + "\n")
         for o in range(res["p"]):
             I, E = res["selection"][o]
             st = int(res["status"][o])
-            if st == 0:
+            if st == 0 and robust:
+                rss = float(res["stats"][o][0])
+                sigma = float(np.sqrt(rss / (len(I) - len(E))))
+                cols = (_g(sigma), _g(rss), _g(float(chi2.sf(rss, len(I) - len(E)))))
+            elif st == 0:
                 rss, sigma = float(res["stats"][o][0]), float(res["stats"][o][1])
                 cols = (_g(sigma), _g(rss), _g(float(chi2.sf(rss, len(I) - len(E)))))
             else:
                 cols = ("NA", "NA", "NA")
             piv = float(res["stats"][o][2])
             tail = ("\t" + (_g(piv) if st in (0, 4) and np.isfinite(piv) else "NA")) if with_ld else ""
+            if robust:
+                r = res["stats"][o]
+                tail += "\t" + ("\t".join((_g(float(r[1])), _g(float(r[2])), str(int(r[4])), _g(float(r[5])))) if st == 0
+                                else "NA\tNA\tNA\tNA")
             f.write(f"{o + 1}\t{len(E)}\t{len(I)}\t" + "\t".join(cols) + f"\t{st}{tail}\n")
+
+
+def write_weights(path: str, res) -> None:
+    """`--robust-weights`: `sink marker rho` for every instrument of an estimated outcome whose final rho is below 1; sink
+    1-based, marker counted from the first marker as in the `Exposure,Outcome,IV` tables"""
+    with open(path, "w") as f:
+        f.write("sink\tmarker\trho\n")
+        for o in range(res["p"]):
+            rho = res["rho"][o]
+            if rho is None:
+                continue
+            I = res["selection"][o][0]
+            for j in np.flatnonzero(np.asarray(rho) < 1.0):
+                f.write(f"{o + 1}\t{int(I[j]) + 1}\t{_g(float(rho[j]))}\n")

@@ -970,6 +970,34 @@ class Engine:
                                         _ptr(stats), _ptr(status), _ptr(ms)))
         return theta, se, stats.reshape(-1)[:3 * nout].reshape(nout, 3), status[:nout], float(ms[0])
 
+    def mvivw_robust(self, beta, weight, outcome, iv_off, iv, ex_off, ex, model=0, psi=2, want_rho=True):
+        """`mvivw` by iteratively reweighted least squares (cusk_mvivw_robust; the rule is stated in include/cusk_hip.h):
+        `psi` 1 Huber, 2 Huber then bisquare.  Returns (theta, se, stats, status, rho, kernel_ms): stats nout x 6 (rss,
+        scale, tau, smallest squared pivot of the last weighted Gram, updates, sum of rho), rho in the layout of `iv`
+        (None unless `want_rho`)."""
+        beta, weight, outcome, iv_off, iv, ex_off, ex, theta, se, _, status = self._mvivw_args(
+            beta, weight, outcome, iv_off, iv, ex_off, ex, None, None, None, None)
+        (M, p), nout = beta.shape, outcome.shape[0]
+        stats = np.full((max(nout, 1), 6), np.nan)
+        rho = np.full(max(int(iv_off.max()), 1), np.nan) if want_rho else None
+        ms = np.zeros(1, np.float32)
+        self._check(lib().cusk_mvivw_robust(self.h, _ptr(beta), _ptr(weight), M, p, nout, _ptr(outcome), _ptr(iv_off), _ptr(iv),
+                                            _ptr(ex_off), _ptr(ex), int(model), int(psi), _ptr(theta), _ptr(se), _ptr(stats),
+                                            _ptr(status), _ptr(rho) if want_rho else None, _ptr(ms)))
+        return theta, se, stats[:nout], status[:nout], rho, float(ms[0])
+
+    def abs_median(self, vals, seg_off, out=None):
+        """The exact median of |vals[seg_off[g]:seg_off[g + 1]]| per segment (cusk_abs_median), NaN for an empty one.
+        `out` may be given (float64, at least one entry per segment) to be filled in place."""
+        vals = np.ascontiguousarray(vals, np.float64).reshape(-1)
+        seg_off = np.ascontiguousarray(seg_off, np.int64).reshape(-1)
+        nseg = seg_off.shape[0] - 1
+        assert nseg >= 0 and vals.shape[0] >= (int(seg_off.max()) if nseg > 0 else 0)
+        out = np.full(max(nseg, 1), np.nan) if out is None else out
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape[0] >= nseg
+        self._check(lib().cusk_abs_median(self.h, _ptr(vals), _ptr(seg_off), nseg, _ptr(out)))
+        return out[:nseg]
+
     def corr_timing(self):
         t = np.zeros(4, np.float32)
         lib().cusk_corr_timing(self.h, _ptr(t))

@@ -788,6 +788,59 @@ int cusk_mvivw_ld(cusk_engine *e, const double *beta, const double *weight, cons
                   int nout, const int *outcome, const long long *iv_off, const int *iv, const int *ex_off, const int *ex, int model,
                   double *theta, double *se, double *stats, int *status, float *kernel_ms);
 
+/* `mvivw --robust`: the regressions of cusk_mvivw made resistant to vertical outliers (instruments with a direct effect
+ * on the outcome) by iteratively reweighted least squares: Huber weights, then optionally Tukey bisquare weights.
+ * NOT the reference's estimator either, and not lmrob, MASS::rlm or the MendelianRandomization package: the reference's
+ * robust = TRUE is an MM-estimator with random subsampling that can be neither run nor restated here.  This is a fully
+ * stated, deterministic M-estimator of the same family, started from the plain fit and not from an S-estimate, so it has
+ * no breakdown guarantee against leverage points.  Nobody has compared it with R.
+ * All pointers are HOST memory.  beta, weight, M, p, outcome, iv_off/iv, ex_off/ex, model, the selections X = beta[I, E],
+ * y = beta[I, o], w = weight[I, o], m = |I|, k = |E|, the argument rules, the chunks of CUSK_MVIVW_CHUNK list positions
+ * and the pivot rule are those of cusk_mvivw.  psi: 1 Huber; 2 Huber, then bisquare from the Huber solution.
+ * The rule per outcome, IEEE double throughout.  The standardised residual of row i at theta is
+ * e_i = sqrt(w_i) (y_i - x_i theta), x_i theta summed over the exposures in list order.
+ *   0. Start: steps 1 - 3 of cusk_mvivw give theta^0, d_j = sqrt(G_jj) and v_j = (G^-1)_jj of the plain weighted Gram;
+ *      statuses 1, 2 and 3 as there.  d and v are kept.
+ *   1. Scale: s = 1.4826 med_i |e_i|, about zero because the regression goes through the origin.  med is the exact
+ *      median of the m absolute values: the middle order statistic, for even m (a + b) * 0.5 of the two middle ones.  It
+ *      is selected on the bit patterns of |e_i|, so it does not depend on any order.  s not > 0: status 6 (more than half
+ *      the rows are fitted exactly).
+ *   2. Huber stage.  With c = 1.345 s, rho_i = 1 where |e_i| <= c, else c / |e_i|.  G_rho = X' diag(w rho) X and
+ *      b_rho = X' diag(w rho) y (each weight is the product w_i rho_i, rounded once) over the same chunks in the same
+ *      order as step 0, solved by step 2 - 3 of cusk_mvivw (its own unit-diagonal scaling and the 1e-8 pivot rule; a
+ *      failure is status 2 and its pivot is reported).  Then e at the new theta and s by step 1 (status 6 applies).
+ *      That is one update t -> t + 1.  The outcome has converged after it when
+ *        max_j d_j |theta_j^{t+1} - theta_j^t| <= 1e-10 s^{t+1} sqrt(m),  d of step 0.
+ *      At most 100 updates; an outcome that has not converged after the 100th is status 5.
+ *   3. Bisquare stage (psi = 2 only), from the Huber solution and its e, with s fixed at the Huber stage's last value:
+ *      u_i = e_i / (4.685 s), rho_i = (1 - u_i^2)^2 where |u_i| < 1, else 0.  The same update, the same stopping rule
+ *      (with the fixed s), its own cap of 100 updates; statuses 2 and 5 as in step 2.
+ *   4. Standard errors, Huber's classical form on the plain Gram.  At the last theta, with its e, the last s and the rho
+ *      of the last stage evaluated at that e (the "final rho"): psi_i = e_i rho_i; psi'_i = 1 where |e_i| <= 1.345 s, else
+ *      0 (Huber); (1 - u_i^2)(1 - 5 u_i^2) where |u_i| < 1, else 0 (bisquare).  A = sum psi_i^2 / (m - k),
+ *      B = sum psi'_i / m, both sums over the chunks in chunk order; tau = sqrt(A) / B; B not > 0: status 5.
+ *      se_j = sqrt(v_j) f with f by model: 1 (random) max(tau, 1); 2 (fixed) max(tau / s, 1); 0 (default) random when
+ *      m >= 4, else fixed.
+ * A converged or failed outcome is frozen: no kernel touches its values again, so they depend neither on the other
+ * outcomes of the call nor on how the outcomes are grouped ("mvivw_part_bytes").  No floating-point atomics: two runs
+ * give the same bytes.
+ * status[a]: 0, 1, 2, 3 as cusk_mvivw; 5 not converged (or B not > 0); 6 the scale is not positive.
+ * Out: theta, se at the positions of ex.  stats nout x 6: the plain rss = sum e_i^2 at the last theta; s; tau; the
+ * smallest squared pivot of the last G_rho; the number of updates of both stages together; sum rho_i (final rho).  rho
+ * (may be NULL; layout of iv, only [iv_off[0], iv_off[nout]) is written): the final rho_i of every row; 0 marks an
+ * instrument the fit rejected.  For a status other than 0 theta, se, the outcome's rho and its stats are NaN, but
+ * stats[3] of status 2 is the pivot that failed (0 for a G_jj that is not positive).
+ * Argument errors (CUSK_ERR_ARG, nothing launched, nothing written): those of cusk_mvivw; psi outside 1 .. 2.
+ * kernel_ms (may be NULL): device time from the first to the last kernel, the reads of the live count included. */
+int cusk_mvivw_robust(cusk_engine *e, const double *beta, const double *weight, long long M, int p, int nout, const int *outcome,
+                      const long long *iv_off, const int *iv, const int *ex_off, const int *ex, int model, int psi, double *theta,
+                      double *se, double *stats, int *status, double *rho, float *kernel_ms);
+/* The selection of step 1 on its own: out[g] = the median of |vals[seg_off[g] .. seg_off[g + 1])|, g = 0 .. nseg - 1, exact
+ * (for an even count (a + b) * 0.5 of the two middle absolute values); NaN for an empty segment.  Host pointers.  The
+ * values are ordered by the bit patterns of their absolute values: -0.0 counts as 0, a NaN lies above every number.
+ * Argument errors: a null pointer, offsets that are negative or not monotone, a segment of 2^31 values or more. */
+int cusk_abs_median(cusk_engine *e, const double *vals, const long long *seg_off, int nseg, double *out);
+
 /* out_host[a*k + b] = M_dev[idx[a]*n + idx[b]]: the retained sub-matrix of parent_set.cpp:84-238
  * (reduce_gc / reduce_gcs) without copying the n*n matrix to the host; idx_host has k entries. */
 int cusk_gather_submatrix(cusk_engine *e, const float *M_dev, int n, const int *idx_host, int k, float *out_host);
