@@ -2,16 +2,12 @@
 // place an engine is opened, a device matrix, and the two read-backs (adjacency bitmap, gathered sub-matrix).  Host code
 // against the C ABI only.
 #pragma once
-#include <cstdint>
 #include <stdexcept>
 #include <string>
-#include <vector>
 
-#include "../../../include/cusk_hip.h"
+#include "result_types.h"
 
 namespace host {
-
-constexpr int ML = CUSK_ML;
 
 // a failed engine call: the CLI prints the message and exits with EXIT_FAILURE (gpuerrors.h:6-15), the library
 // entry points return CUSK_ERR_* with the message retrievable
@@ -32,13 +28,6 @@ inline cusk_engine *open_engine()
     if (cusk_engine_create(&e, 0, nullptr) != CUSK_OK) engine_die("engine create (is a HIP device visible?)", nullptr);
     return e;
 }
-
-struct Bits
-{
-    int n = 0, words = 0;
-    std::vector<uint64_t> w;
-    bool get(int i, int j) const { return (w[(size_t)i * words + (j >> 6)] >> (j & 63)) & 1ull; }
-};
 
 inline Bits fetch_adjacency(cusk_engine *e)
 {

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "batch_plan.h"
 #include "engine_util.h"
 #include "host_io.h"
 
@@ -82,15 +83,7 @@ inline std::vector<int> compose(const std::vector<int> &P, const std::vector<int
     return out;
 }
 
-// ReducedGC / ReducedGCS of include/mps/parent_set.h
-// One separating set of the reduced result: the cell (ix, iy) of the num_var x num_var x max_level array holds s[0 .. cnt)
-// followed by -1
-struct SepRec
-{
-    int ix, iy, cnt;
-    int s[ML];
-};
-
+// ReducedGC / ReducedGCS of include/mps/parent_set.h (SepRec, one separating set of it: result_types.h)
 struct Reduced
 {
     size_t num_var = 0, num_phen = 0, max_level = 0;
@@ -118,14 +111,7 @@ struct Reduced
     }
 };
 
-// arrival order -> ascending cells; records of one cell keep their order (the later one overwrites the head of the earlier,
-// as in the dense reduction)
-inline void sort_sep_recs(Reduced &r)
-{
-    const size_t k = r.num_var;
-    auto less = [k](const SepRec &a, const SepRec &b) { return (size_t)a.ix * k + (size_t)a.iy < (size_t)b.ix * k + (size_t)b.iy; };
-    if (!std::is_sorted(r.sep_recs.begin(), r.sep_recs.end(), less)) std::stable_sort(r.sep_recs.begin(), r.sep_recs.end(), less);
-}
+inline void sort_sep_recs(Reduced &r) { sort_recs(r.sep_recs, r.num_var); }
 
 // The .sep file of a sparse result: the array goes out in pieces of ~1 MB that are a whole number of cells, from ONE buffer
 // of -1 that is patched with the sets of the piece and restored afterwards -- no 18 MB array to fill and to read back
@@ -175,92 +161,28 @@ inline void write_reduced(const Reduced &r, const std::string &base, bool with_s
         write_binary(base + ".sep", r.S.data(), r.S.size());
 }
 
-// parent_set.cpp:84-175 on sparse records.  Entries of a set that are not retained are dropped, the
-// rest is compacted and padded with -1 to `max_level`; at most `max_level` source entries are read.
-// With an index_map (stage two) the reference keys old_to_new by index_map[P[i]] although the set
-// members are still in the P index space: a member that is not a key maps to 0.
+// parent_set.cpp:84-175 on the sparse records of the engine's last run.  Entries of a set that are not retained are dropped,
+// the rest is compacted and padded with -1 to `max_level`; at most `max_level` source entries are read.  With an index_map
+// (stage two) the reference keys old_to_new by index_map[P[i]] although the set members are still in the P index space
+// (SURVEY App. C.3): a member that is not a key maps to 0.  The rule itself: remap_sepset of batch_plan.h.
 inline std::vector<int> reduce_sepsets(cusk_engine *e, const std::vector<int> &P, size_t max_level,
                                        const std::vector<int> *index_map)
 {
-    const size_t k = P.size();
-    std::vector<int> S(k * k * max_level, -1);
     const int *x = nullptr, *y = nullptr, *rs = nullptr;  // engine-owned pinned memory
     const long long cnt = cusk_result_sepsets_view(e, &x, &y, &rs);
     if (cnt < 0) engine_die("sepsets", e);
-    if (cnt == 0) return S;
-    std::unordered_map<int, int> pos, old_to_new;
-    for (size_t i = 0; i < k; i++)
-    {
-        pos[P[i]] = (int)i;
-        old_to_new[index_map ? (*index_map)[P[i]] : P[i]] = (int)i;
-    }
-    for (long long r = 0; r < cnt; r++)
-    {
-        auto ix = pos.find(x[r]), iy = pos.find(y[r]);
-        if (ix == pos.end() || iy == pos.end()) continue;
-        int *dst = &S[((size_t)ix->second * k + iy->second) * max_level];
-        size_t c = 0;
-        for (size_t l = 0; l < max_level && l < (size_t)ML; l++)
-        {
-            const int sv = rs[(size_t)r * ML + l];
-            if (sv != -1 && pos.count(sv))
-            {
-                auto it = old_to_new.find(sv);
-                dst[c++] = (it == old_to_new.end()) ? 0 : it->second;
-            }
-        }
-    }
-    return S;
+    return reduce_records(cnt, x, y, rs, cusk_result_n(e), P, max_level, index_map);
 }
 
-// reduce_sepsets without the dense array: the same cells as a list in ascending (ix, iy) order.  Returns false (and leaves
-// the list empty) when two records name the same cell -- the dense form's "the later record overwrites the head of the
-// earlier" is then what the caller must reproduce (never seen: an ordered pair has one record).
+// reduce_sepsets without the dense array: the same cells as a list in ascending (ix, iy) order; false (and an empty list)
+// when two records name the same cell (reduce_records_sparse)
 inline bool reduce_sepsets_sparse(cusk_engine *e, const std::vector<int> &P, size_t max_level, const std::vector<int> *index_map,
                                   std::vector<SepRec> &out)
 {
-    out.clear();
-    const size_t k = P.size();
     const int *x = nullptr, *y = nullptr, *rs = nullptr;  // engine-owned pinned memory
     const long long cnt = cusk_result_sepsets_view(e, &x, &y, &rs);
     if (cnt < 0) engine_die("sepsets", e);
-    if (cnt == 0) return true;
-    std::unordered_map<int, int> pos, old_to_new;
-    for (size_t i = 0; i < k; i++)
-    {
-        pos[P[i]] = (int)i;
-        old_to_new[index_map ? (*index_map)[P[i]] : P[i]] = (int)i;
-    }
-    out.reserve((size_t)cnt);
-    for (long long r = 0; r < cnt; r++)
-    {
-        auto ix = pos.find(x[r]), iy = pos.find(y[r]);
-        if (ix == pos.end() || iy == pos.end()) continue;
-        SepRec q;
-        q.ix = ix->second;
-        q.iy = iy->second;
-        q.cnt = 0;
-        for (size_t l = 0; l < max_level && l < (size_t)ML; l++)
-        {
-            const int sv = rs[(size_t)r * ML + l];
-            if (sv != -1 && pos.count(sv))
-            {
-                auto it = old_to_new.find(sv);
-                q.s[q.cnt++] = (it == old_to_new.end()) ? 0 : it->second;
-            }
-        }
-        out.push_back(q);
-    }
-    auto key = [k](const SepRec &q) { return (size_t)q.ix * k + (size_t)q.iy; };
-    if (!std::is_sorted(out.begin(), out.end(), [&](const SepRec &a, const SepRec &b) { return key(a) < key(b); }))
-        std::stable_sort(out.begin(), out.end(), [&](const SepRec &a, const SepRec &b) { return key(a) < key(b); });
-    for (size_t i = 1; i < out.size(); i++)
-        if (key(out[i]) == key(out[i - 1]))
-        {
-            out.clear();
-            return false;
-        }
-    return true;
+    return reduce_records_sparse(cnt, x, y, rs, cusk_result_n(e), P, max_level, index_map, out);
 }
 
 }  // namespace host
