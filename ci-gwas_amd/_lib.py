@@ -166,6 +166,8 @@ SYMBOLS = {
     "cusk_iv_check": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cusk_iv_check_het": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp, _ll, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp]),
     "cusk_mvivw": (_i, [_vp, _vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cusk_mvivw_jackknife": (_i, [_vp, _vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _vp]),
     "cusk_mvivw_robust": (_i, [_vp, _vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cusk_abs_median": (_i, [_vp, _vp, _vp, _i, _vp]),
     "cusk_mvivw_ld": (_i, [_vp, _vp, _vp, _vp, C.c_double, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -308,6 +308,20 @@ def _add_mvivw(sub):
                         "not the reference's lmrob.  <stem>_mvivw_outcomes.tsv gains the columns scale tau iterations rho_sum")
     p.add_argument("--robust-weights", metavar="FILE", type=str, default=None,
                    help="with --robust: write sink, marker, rho of every instrument whose final weight rho is below 1")
+    jk = p.add_mutually_exclusive_group()
+    jk.add_argument("--jackknife", metavar="loo|B", type=str, default=None,
+                    help="refit every outcome without each group of its instruments: loo = one group per instrument (the "
+                         "leave-one-out table and PRESS), B >= 2 = that many contiguous groups of the instrument list (the "
+                         "delete-one-block jackknife, whose standard error needs no LD matrix).  <stem>_mvivw_results.tsv gains "
+                         "the columns jk_effect jk_se jk_p jk_min jk_max jk_marker, <stem>_mvivw_outcomes.tsv jk_groups press "
+                         "jk_pivot jk_status.  Not MR-PRESSO: no simulated null, no p-value of the global test")
+    jk.add_argument("--jackknife-groups", metavar="FILE", type=str, default=None,
+                    help="the same with groups from FILE: one non-decreasing integer label per marker row (LD blocks); a "
+                         "group is a run of instruments with one label")
+    p.add_argument("--jackknife-residuals", metavar="FILE", type=str, default=None,
+                   help="with --jackknife / --jackknife-groups: write sink, marker, group, press_residual of every instrument")
+    p.add_argument("--jackknife-table", metavar="FILE", type=str, default=None,
+                   help="with --jackknife / --jackknife-groups: write the estimates without each group")
     p.add_argument("--out", type=str, default=None, help="output file (default <cusk-output-stem>_mvivw_results.tsv)")
     p.set_defaults(func=run_mvivw, parser=p)
 
@@ -621,17 +635,34 @@ def run_mvivw(args):
                           "has no meaning there")
     if args.robust_weights and not args.robust:
         args.parser.error("--robust-weights needs --robust")
+    with_jk = args.jackknife is not None or args.jackknife_groups is not None
+    if with_jk and (args.ld or args.robust):
+        args.parser.error("--jackknife cannot be combined with --ld or --robust: whitening mixes the rows, and a reweighted "
+                          "refit per deletion is another estimator")
+    if (args.jackknife_residuals or args.jackknife_table) and not with_jk:
+        args.parser.error("--jackknife-residuals and --jackknife-table need --jackknife or --jackknife-groups")
+    jackknife = None
+    if args.jackknife is not None:
+        if args.jackknife != "loo" and not (args.jackknife.isdigit() and int(args.jackknife) >= 2):
+            args.parser.error("--jackknife takes loo or a number of groups >= 2")
+        jackknife = "loo" if args.jackknife == "loo" else int(args.jackknife)
     data = load(stem, het=args.het)  # unreadable inputs are reported before an engine exists; read once
+    if args.jackknife_groups is not None:
+        jackknife = mvivw.read_group_labels(args.jackknife_groups, data[0].shape[0] - data[2])
     write_csv(f"{stem}_iv_candidates.csv", iv_candidates(stem, data=data))
     mode = "skeleton" if args.s else "prior" if args.orientation_prior else "ivs" if args.ivs else "all"
     res = mvivw.run(stem, args.num_samples, mode=mode, prior_path=args.orientation_prior, ivs_path=args.ivs, het=args.het,
                     model=mvivw.MODELS[args.model], engine=_mvivw_engine(), data=data, ld=args.ld, ld_ridge=args.ld_ridge or 0.0,
-                    robust=args.robust)
+                    robust=args.robust, jackknife=jackknife)
     out = args.out or f"{stem}_mvivw_results.tsv"
     mvivw.write_results(out, res)
     mvivw.write_outcomes(f"{out[:-len('_results.tsv')]}_outcomes.tsv" if out.endswith("_results.tsv") else f"{out}.outcomes.tsv", res)
     if args.robust_weights:
         mvivw.write_weights(args.robust_weights, res)
+    if args.jackknife_residuals:
+        mvivw.write_jackknife_residuals(args.jackknife_residuals, res)
+    if args.jackknife_table:
+        mvivw.write_jackknife_table(args.jackknife_table, res)
     print(f"mvivw: {int((res['status'] == 0).sum())} of {res['p']} outcomes estimated.")
 
 

@@ -226,6 +226,7 @@ struct cusk_engine
     long long opt_sep_ws_budget = 4ll << 30;  // HBM work space of cusk_sepselect_greedy for candidate lists beyond LDS
     long long opt_mvivw_ld_bytes = 8ll << 30;  // HBM of cusk_mvivw_ld's m x m workspace (kLdBytes of host/mvivw_ld_plan.h)
     long long opt_mvivw_part_bytes = 256ll << 20;  // HBM of cusk_mvivw's chunk partials alive at once (kMvPartBound of host/mvivw_plan.h)
+    long long opt_mvivw_jk_bytes = 1ll << 30;  // HBM of cusk_mvivw_jackknife's refitted estimates alive at once (kMvJkBytes of host/mvivw_jk_plan.h)
     long long opt_phen_rint_bytes = 1ll << 30;  // HBM of cusk_phen_rint's keys and ranks alive at once: traits run in groups of what fits
 
     // row-sharded sweep of ONE block over several engines: this engine runs the tests of rows

@@ -202,6 +202,8 @@ extern "C" int cusk_engine_set_option(cusk_engine *e, const char *key, long long
         e->opt_mvivw_part_bytes = value;
     else if (k == "mvivw_ld_bytes" && value > 0)
         e->opt_mvivw_ld_bytes = value;
+    else if (k == "mvivw_jk_bytes" && value > 0)
+        e->opt_mvivw_jk_bytes = value;
     else if (k == "phen_rint_bytes" && value > 0)
         e->opt_phen_rint_bytes = value;
     else

@@ -121,76 +121,20 @@ __global__ void __launch_bounds__(256) mv_solve_kernel(MvBatch b, int first)
             L[e] = s;
         else
             bv[e - EL] = s;
+        if (b.gsum) b.gsum[(size_t)slot * kMvSumLd + e] = s;
     }
     __syncthreads();
-    int nonpos = 0;
-    if (tid < k)
+    double minpiv;
+    const int rc = mv_factor_solve(L, d, bv, x, k, &minpiv);  // the same for every thread
+    if (b.dsc && rc != 1 && tid < k) b.dsc[(size_t)slot * kMvVec + tid] = d[tid];
+    if (rc != 0)
     {
-        const double g = L[tid * (tid + 1) / 2 + tid];
-        nonpos = !(g > 0.0);
-        d[tid] = sqrt(g);
-    }
-    if (__syncthreads_or(nonpos))
-    {  // a column of zeros
         if (tid == 0)
         {
             b.status[slot] = 2;
-            sol[2 * kMvVec] = 0.0;
+            sol[2 * kMvVec] = minpiv;  // the pivot that failed, 0 for a G_jj that is not positive
         }
         return;
-    }
-    if (b.dsc && tid < k) b.dsc[(size_t)slot * kMvVec + tid] = d[tid];
-    if (tid < k)
-    {
-        const int rr = tid * (tid + 1) / 2;
-        for (int c = 0; c < tid; c++) L[rr + c] = L[rr + c] / (d[tid] * d[c]);
-        L[rr + tid] = 1.0;
-    }
-    __syncthreads();
-    double minpiv = INFINITY;
-    const int tr = tid >> 4, tc = tid & 15;
-    for (int j = 0; j < k; j++)
-    {
-        const int jj = j * (j + 1) / 2 + j;
-        const double piv = L[jj];
-        if (!(piv >= minpiv)) minpiv = piv;
-        if (!(piv >= kMvPivotMin))
-        {  // the same for every thread
-            if (tid == 0)
-            {
-                b.status[slot] = 2;
-                sol[2 * kMvVec] = piv;
-            }
-            return;
-        }
-        const double l = sqrt(piv);
-        __syncthreads();
-        if (tid == 0) L[jj] = l;
-        for (int r = j + 1 + tid; r < k; r += 256) L[r * (r + 1) / 2 + j] /= l;
-        __syncthreads();
-        for (int r = j + 1 + tr; r < k; r += 16)
-        {
-            const int rr = r * (r + 1) / 2;
-            const double lrj = L[rr + j];
-            for (int c = j + 1 + tc; c <= r; c += 16) L[rr + c] = fma(-lrj, L[c * (c + 1) / 2 + j], L[rr + c]);
-        }
-        __syncthreads();
-    }
-    // L w = D^-1 b, thread r owns row r
-    double rhs = tid < k ? bv[tid] / d[tid] : 0.0;
-    for (int j = 0; j < k; j++)
-    {
-        if (tid == j) x[j] = rhs / L[j * (j + 1) / 2 + j];
-        __syncthreads();
-        if (tid > j && tid < k) rhs = fma(-L[tid * (tid + 1) / 2 + j], x[j], rhs);
-    }
-    // L' u = w; u goes to bv, which has been read
-    rhs = tid < k ? x[tid] : 0.0;
-    for (int j = k - 1; j >= 0; j--)
-    {
-        if (tid == j) bv[j] = rhs / L[j * (j + 1) / 2 + j];
-        __syncthreads();
-        if (tid < j) rhs = fma(-L[j * (j + 1) / 2 + tid], bv[j], rhs);
     }
     // the inverse of L in place, last column first: X_jj = 1 / L_jj, X_ij = -(sum_{c = j+1..i} X_ic L_cj) / L_jj
     for (int j = k - 1; j >= 0; j--)
@@ -336,6 +280,29 @@ void launch_mv_gram(hipStream_t s, const MvBatch &b, int cls, const MvChunk *chu
         launch_mv_gram_form<false>(s, b, cls, chunks, cnt);
 }
 
+hipError_t mv_plain_enqueue(hipStream_t s, const MvBatch &b, const MvPlan &plan, const MvChunk *chunks)
+{
+    for (const MvGroup &g : plan.groups)
+    {  // one stream: the partials of a group are read before the next group's Gram kernels overwrite them
+        for (int c = 0; c < kMvClasses; c++)
+        {
+            const size_t cnt = g.class_first[c + 1] - g.class_first[c];
+            if (cnt == 0) continue;
+            launch_mv_gram(s, b, c, chunks + g.class_first[c], cnt, false);
+            if (hipError_t st = hipGetLastError(); st != hipSuccess) return st;
+        }
+        const unsigned nslots = (unsigned)(g.last - g.first);
+        const size_t nchunks = g.class_first[kMvClasses] - g.class_first[0];
+        launch_mv_solve(s, b, g.first, nslots);
+        if (hipError_t st = hipGetLastError(); st != hipSuccess) return st;
+        hipLaunchKernelGGL(mv_resid_kernel, dim3((unsigned)nchunks), dim3(256), 0, s, b, chunks + g.class_first[0]);
+        if (hipError_t st = hipGetLastError(); st != hipSuccess) return st;
+        launch_mv_finish(s, b, g.first, nslots);
+        if (hipError_t st = hipGetLastError(); st != hipSuccess) return st;
+    }
+    return hipSuccess;
+}
+
 namespace {
 
 int mvivw_impl(cusk_engine *e, const double *beta, const double *weight, long long M, int p, int nout, const int *outcome,
@@ -384,25 +351,7 @@ int mvivw_impl(cusk_engine *e, const double *beta, const double *weight, long lo
         CUSK_HIP(e, res.alloc(b));
         CUSK_HIP(e, mv_reg_prepare());
         CUSK_HIP(e, evs.record(0, s));
-        const MvChunk *chunks = d_chunks.as<MvChunk>();
-        for (const MvGroup &g : plan.groups)
-        {  // one stream: the partials of a group are read before the next group's Gram kernels overwrite them
-            for (int c = 0; c < kMvClasses; c++)
-            {
-                const size_t cnt = g.class_first[c + 1] - g.class_first[c];
-                if (cnt == 0) continue;
-                launch_mv_gram(s, b, c, chunks + g.class_first[c], cnt, false);
-                CUSK_HIP(e, hipGetLastError());
-            }
-            const unsigned nslots = (unsigned)(g.last - g.first);
-            const size_t nchunks = g.class_first[kMvClasses] - g.class_first[0];
-            launch_mv_solve(s, b, g.first, nslots);
-            CUSK_HIP(e, hipGetLastError());
-            hipLaunchKernelGGL(mv_resid_kernel, dim3((unsigned)nchunks), dim3(256), 0, s, b, chunks + g.class_first[0]);
-            CUSK_HIP(e, hipGetLastError());
-            launch_mv_finish(s, b, g.first, nslots);
-            CUSK_HIP(e, hipGetLastError());
-        }
+        CUSK_HIP(e, mv_plain_enqueue(s, b, plan, d_chunks.as<MvChunk>()));
         CUSK_HIP(e, evs.record(1, s));
         CUSK_HIP(e, res.read_back(s));
         CUSK_HIP(e, hipStreamSynchronize(s));

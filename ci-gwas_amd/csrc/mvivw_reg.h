@@ -17,6 +17,7 @@ namespace cusk {
 constexpr int kMvTriMax = kMvMaxExposures * (kMvMaxExposures + 1) / 2;  // 8128 doubles: 63.5 KB
 constexpr int kMvVec = 128;
 constexpr int kMvSolLd = 2 * kMvVec + 1;  // per active outcome: theta[128], v[128], the smallest squared pivot
+constexpr int kMvSumLd = kMvTriMax + kMvVec;  // per active outcome: the summed triangle G packed by rows, then b (MvBatch::gsum)
 constexpr double kMvPivotMin = CUSK_PHEN_PIVOT_MIN;
 constexpr double kMvNaN = std::numeric_limits<double>::quiet_NaN();
 // LDS carve of the solve kernel (doubles): L[kMvTriMax], d[128], bv[128], x[128]
@@ -45,6 +46,9 @@ struct MvBatch
     const double *rho = nullptr;  // layout of iv: the Gram kernel multiplies the weight of a list position by it
     const int *frozen = nullptr;  // per active outcome: not 0 = the Gram (rho form) and solve kernels leave it as it is
     double *dsc = nullptr;        // per active outcome: kMvVec doubles, the solve kernel's d_j = sqrt(G_jj)
+    // mvivw_jackknife.hip alone sets this; null: the sums stay in LDS
+    double *gsum = nullptr;  // per active outcome: kMvSumLd doubles, the chunk-ordered sums the solve kernel forms: the lower
+                             // triangle of G packed by rows (k (k + 1) / 2 doubles), then b (k doubles)
 };
 
 __device__ __forceinline__ bool mv_finite(double v) { return fabs(v) <= DBL_MAX; }  // false for NaN
@@ -104,6 +108,79 @@ __device__ __forceinline__ double mv_block_sum(double term, double *sh)
     return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
+// Steps 2 - 3 of the rule for one system in LDS, called by every thread of a workgroup of 256 with the same arguments
+// (mv_solve_kernel, and mv_jk_refit_kernel of mvivw_jackknife.hip for the downdated systems).  In: L the lower triangle
+// of G packed by rows, bv = b.  d_j = sqrt(G_jj), the unit-diagonal scaling, the right-looking Cholesky with the pivot
+// test, both substitutions.  Returns 0 with *piv the smallest squared pivot, L the factor of the scaled Gram and bv = u,
+// theta_j = u_j / d_j; 1 for a G_jj that is not positive (*piv = 0; d is not usable); 2 for a squared pivot below
+// kMvPivotMin (*piv = that pivot).  x: k doubles of scratch.  The caller has synchronised after writing L and bv.
+__device__ __forceinline__ int mv_factor_solve(double *L, double *d, double *bv, double *x, int k, double *piv)
+{
+    const int tid = threadIdx.x;
+    int nonpos = 0;
+    if (tid < k)
+    {
+        const double g = L[tid * (tid + 1) / 2 + tid];
+        nonpos = !(g > 0.0);
+        d[tid] = sqrt(g);
+    }
+    if (__syncthreads_or(nonpos))
+    {  // a column of zeros
+        *piv = 0.0;
+        return 1;
+    }
+    if (tid < k)
+    {
+        const int rr = tid * (tid + 1) / 2;
+        for (int c = 0; c < tid; c++) L[rr + c] = L[rr + c] / (d[tid] * d[c]);
+        L[rr + tid] = 1.0;
+    }
+    __syncthreads();
+    double minpiv = INFINITY;
+    const int tr = tid >> 4, tc = tid & 15;
+    for (int j = 0; j < k; j++)
+    {
+        const int jj = j * (j + 1) / 2 + j;
+        const double pv = L[jj];
+        if (!(pv >= minpiv)) minpiv = pv;
+        if (!(pv >= kMvPivotMin))
+        {  // the same for every thread
+            *piv = pv;
+            return 2;
+        }
+        const double l = sqrt(pv);
+        __syncthreads();
+        if (tid == 0) L[jj] = l;
+        for (int r = j + 1 + tid; r < k; r += 256) L[r * (r + 1) / 2 + j] /= l;
+        __syncthreads();
+        for (int r = j + 1 + tr; r < k; r += 16)
+        {
+            const int rr = r * (r + 1) / 2;
+            const double lrj = L[rr + j];
+            for (int c = j + 1 + tc; c <= r; c += 16) L[rr + c] = fma(-lrj, L[c * (c + 1) / 2 + j], L[rr + c]);
+        }
+        __syncthreads();
+    }
+    // L w = D^-1 b, thread r owns row r
+    double rhs = tid < k ? bv[tid] / d[tid] : 0.0;
+    for (int j = 0; j < k; j++)
+    {
+        if (tid == j) x[j] = rhs / L[j * (j + 1) / 2 + j];
+        __syncthreads();
+        if (tid > j && tid < k) rhs = fma(-L[tid * (tid + 1) / 2 + j], x[j], rhs);
+    }
+    // L' u = w; u goes to bv, which has been read
+    rhs = tid < k ? x[tid] : 0.0;
+    for (int j = k - 1; j >= 0; j--)
+    {
+        if (tid == j) bv[j] = rhs / L[j * (j + 1) / 2 + j];
+        __syncthreads();
+        if (tid < j) rhs = fma(-L[j * (j + 1) / 2 + tid], bv[j], rhs);
+    }
+    *piv = minpiv;
+    return 0;
+}
+
 // mvivw.hip: mv_solve_kernel and mv_finish_kernel for the active outcomes first .. first + nslots - 1 of b.outs.  A
 // kernel is launched only from the file that defines it; the caller asks hipGetLastError.
 hipError_t mv_reg_prepare();  // once per call, before the first launch: the dynamic LDS of the solve kernel
@@ -112,6 +189,9 @@ void launch_mv_finish(hipStream_t s, const MvBatch &b, int first, unsigned nslot
 // mv_gram_kernel of tile class `cls` for `cnt` chunks; with_rho: the form that multiplies every weight by b.rho and
 // skips the chunks of frozen outcomes (mvivw_robust.hip)
 void launch_mv_gram(hipStream_t s, const MvBatch &b, int cls, const MvChunk *chunks, size_t cnt, bool with_rho);
+// the plain regressions of every group of the plan, enqueued on s: Gram by class, solve, residuals, finish.  chunks: the
+// plan's chunks on the device.  What cusk_mvivw runs, and step 0 of cusk_mvivw_jackknife.
+hipError_t mv_plain_enqueue(hipStream_t s, const MvBatch &b, const MvPlan &plan, const MvChunk *chunks);
 
 // What the two entry points keep per call beside their tables: the device arrays the solve and finish kernels write,
 // per active outcome (na) and per exposure position (nex), and their host copies.

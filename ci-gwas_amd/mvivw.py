@@ -71,6 +71,21 @@ def read_ivs(path: str):
     return rows
 
 
+def read_group_labels(path: str, M: int):
+    """`--jackknife-groups FILE`: M lines, one non-decreasing integer label per marker row"""
+    with open(path) as f:
+        words = f.read().split()
+    try:
+        labels = np.array([int(v) for v in words], np.int64)
+    except ValueError:
+        raise ValueError(f"{path}: a label is not an integer") from None
+    if labels.shape[0] != M:
+        raise ValueError(f"{path}: expected {M} labels, one per marker row, found {labels.shape[0]}")
+    if np.any(np.diff(labels) < 0):
+        raise ValueError(f"{path}: the labels are not non-decreasing")
+    return labels
+
+
 def select(adj, p: int, mode: str = "all", prior=None, iv_rows=None):
     """[(I, E)] per outcome: ascending int arrays of marker rows and exposure traits"""
     adj = np.asarray(adj)
@@ -135,16 +150,39 @@ def check_arguments(M, p, outcome, iv_off, iv, ex_off, ex, model):
             raise ValueError(f"mvivw: outcome {a}: the exposure list is not strictly ascending inside [0, p) without the outcome")
 
 
-def _gram_solve(Z, w):
-    """Steps 1 - 3 of the rule for Z = (X, y) with the row weights w -> (status 0 | 2, theta, v, d, pivot): the smallest
-    squared pivot, or the one that failed (0 for a G_jj that is not positive)"""
-    from scipy.linalg import solve_triangular
-
+def _gram_sums(Z, w):
+    """Step 1 of the rule: Z'WZ for Z = (X, y), chunk partials added in chunk order"""
     m, k = Z.shape[0], Z.shape[1] - 1
     S = np.zeros((k + 1, k + 1), Z.dtype)
-    for c0 in range(0, m, CHUNK):  # chunk partials, added in chunk order
+    for c0 in range(0, m, CHUNK):
         Zc = Z[c0:c0 + CHUNK]
         S += (Zc * w[c0:c0 + CHUNK, None]).T @ Zc
+    return S
+
+
+def _tri_solve(L, b, trans: bool):
+    """L x = b (trans: L' x = b) for a lower triangular L, in the type of L"""
+    if L.dtype == np.float64:
+        from scipy.linalg import solve_triangular
+
+        return solve_triangular(L, b, lower=True, trans=1 if trans else 0)
+    k = L.shape[0]
+    x = b.copy()  # scipy has no solver of the extended type: by columns
+    for j in (range(k - 1, -1, -1) if trans else range(k)):
+        x[j] = x[j] / L[j, j]
+        if trans:
+            x[:j] -= L[j, :j] * x[j]
+        else:
+            x[j + 1:] -= L[j + 1:, j] * x[j]
+    return x
+
+
+def _solve_sums(S, want_v: bool = True):
+    """Steps 2 - 3 of the rule for the sums S = Z'WZ -> (status 0 | 2, theta, v, d, pivot): the smallest squared pivot, or
+    the one that failed (0 for a G_jj that is not positive).  want_v False: v is None, theta by two substitutions"""
+    from scipy.linalg import solve_triangular
+
+    k = S.shape[0] - 1
     G, b = S[:k, :k], S[k, :k]
     dg = np.diag(G)
     if not (dg > 0).all():
@@ -161,10 +199,12 @@ def _gram_solve(Z, w):
         L[j, j] = np.sqrt(piv)
         L[j + 1:, j] /= L[j, j]
         L[j + 1:, j + 1:] -= np.tril(np.outer(L[j + 1:, j], L[j + 1:, j]))
-    if Z.dtype == np.float64:
+    if not want_v:
+        return 0, _tri_solve(L, _tri_solve(L, b / d, False), True) / d, None, d, float(minpiv)
+    if S.dtype == np.float64:
         Linv = solve_triangular(L, np.eye(k), lower=True)
     else:  # the extended-precision restatement of the tests: scipy has no such solver
-        Linv = np.zeros((k, k), Z.dtype)
+        Linv = np.zeros((k, k), S.dtype)
         for j in range(k):
             Linv[j, j] = 1 / L[j, j]
             for i in range(j + 1, k):
@@ -172,6 +212,12 @@ def _gram_solve(Z, w):
     theta = (Linv.T @ (Linv @ (b / d))) / d
     v = (Linv * Linv).sum(axis=0) / (d * d)
     return 0, theta, v, d, float(minpiv)
+
+
+def _gram_solve(Z, w):
+    """Steps 1 - 3 of the rule for Z = (X, y) with the row weights w -> (status 0 | 2, theta, v, d, pivot): the smallest
+    squared pivot, or the one that failed (0 for a G_jj that is not positive)"""
+    return _solve_sums(_gram_sums(Z, w))
 
 
 def solve_one(X, y, w, model: int):
@@ -286,6 +332,112 @@ def solve_one_robust(X, y, w, model: int, psi: int, max_updates: int = MAX_UPDAT
     return 0, theta, se, (_chunk_sum(e * e), s, tau, piv, updates, _chunk_sum(rho)), rho
 
 
+JK_CHUNK = 256  # kMvJkChunk of csrc/host/mvivw_jk_plan.h: groups per chunk of the sums over groups
+
+
+def groups(I, spec, labels=None):
+    """The group boundaries of an instrument list I (ascending marker rows) for `cusk_mvivw_jackknife`: list positions,
+    strictly ascending from 0 to m = len(I).  spec "loo": one group per instrument; an integer B >= 2: boundary
+    g = floor(g m / B), B capped at m; "labels": `labels` holds a non-decreasing integer per marker row and the boundaries
+    fall where the label changes along I.  An empty list gives the single boundary 0."""
+    m = len(I)
+    if spec == "loo":
+        return np.arange(m + 1, dtype=np.int32)
+    if spec == "labels":
+        lab = np.asarray(labels)
+        if lab.ndim != 1 or lab.dtype.kind not in "iu":
+            raise ValueError("mvivw: the group labels are not a list of integers")
+        if np.any(np.diff(lab) < 0):
+            raise ValueError("mvivw: the group labels are not non-decreasing")
+        if m and (int(np.min(I)) < 0 or int(np.max(I)) >= lab.shape[0]):
+            raise ValueError("mvivw: an instrument has no group label")
+        li = lab[np.asarray(I, np.int64)]
+        return np.concatenate([[0], np.flatnonzero(np.diff(li) != 0) + 1, [m]] if m else [[0]]).astype(np.int32)
+    if isinstance(spec, (bool, np.bool_)) or not isinstance(spec, (int, np.integer)) or spec < 2:
+        raise ValueError(f"mvivw: jackknife {spec!r} is not loo, labels or a number of groups >= 2")
+    B = min(int(spec), m)
+    return np.array([g * m // B for g in range(B + 1)] if m else [0], dtype=np.int32)
+
+
+def check_groups(iv_off, ex_off, grp_off, grp):
+    """the argument errors `cusk_mvivw_jackknife` adds to those of cusk_mvivw (csrc/host/mvivw_jk_plan.h), as a ValueError"""
+    if grp_off is None:
+        raise ValueError("mvivw: no group offsets")
+    if len(grp_off) != len(iv_off) or np.any(np.diff(grp_off) < 0) or (len(grp_off) and grp_off[0] < 0):
+        raise ValueError("mvivw: group offsets are not monotone")
+    for a in range(len(iv_off) - 1):
+        m, b = int(iv_off[a + 1] - iv_off[a]), grp[grp_off[a]:grp_off[a + 1]]
+        if m > 0 and len(b) < 2:
+            raise ValueError(f"mvivw: outcome {a}: instruments and no groups")
+        if len(b) and (b[0] != 0 or b[-1] != m or np.any(np.diff(b) <= 0)):
+            raise ValueError(f"mvivw: outcome {a}: the group boundaries are not strictly ascending from 0 to m")
+
+
+def _group_sum(t):
+    """a sum over groups: chunks of JK_CHUNK groups, inside a chunk in ascending order, the chunk sums in chunk order"""
+    tot = np.zeros(t.shape[1:], t.dtype)
+    for c0 in range(0, t.shape[0], JK_CHUNK):
+        s = np.zeros(t.shape[1:], t.dtype)
+        for row in t[c0:c0 + JK_CHUNK]:
+            s = s + row
+        tot = tot + s
+    return tot
+
+
+def solve_one_jackknife(X, y, w, bounds, model: int):
+    """One problem of `cusk_mvivw_jackknife` by the rule of include/cusk_hip.h, in the floating-point type of X (float64;
+    the tests restate it in np.longdouble by passing such arrays).  bounds: the ng + 1 group boundaries.
+    -> (status, theta, se, (rss, sigma, pivot), jk_status, jk (k x 4: theta_J, se_J, min, max) | None, jk_arg | None,
+    (press, pivot), pres | None, refit (ng x k) | None)"""
+    m, k = X.shape
+    ft = X.dtype.type
+    bounds = np.asarray(bounds, np.int64)
+    none = (None, None, (np.nan, np.nan), None, None)
+    nan3 = (np.nan, np.nan, np.nan)
+    if k == 0 or m <= k:
+        return (1, None, None, nan3, 1) + none
+    if not (np.isfinite(X).all() and np.isfinite(y).all() and np.isfinite(w).all() and (w > 0).all()):
+        return (3, None, None, nan3, 3) + none
+    Z = np.concatenate([X, y[:, None]], axis=1)
+    S = _gram_sums(Z, w)
+    st, theta, v, _, minpiv = _solve_sums(S)
+    if st != 0:
+        return (st, None, None, (np.nan, np.nan, minpiv), st) + none
+    r = y - X @ theta
+    rss = _chunk_sum(w * (r * r))
+    sigma = np.sqrt(rss / ft(m - k))
+    random = model == 1 or (model == 0 and m >= 4)
+    se = np.sqrt(v) * (sigma if random and sigma > 1 else ft(1))
+    plain = (0, theta, se, (rss, sigma, minpiv))
+    ng = len(bounds) - 1
+    mg = np.diff(bounds)
+    if ng < 2 or np.any(m - mg <= k):
+        return plain + (1,) + none
+    sw = np.sqrt(w)
+    refit, pres, gpress = np.zeros((ng, k), X.dtype), np.zeros(m, X.dtype), np.zeros(ng, X.dtype)
+    jpiv = np.inf
+    for g in range(ng):
+        r0, r1 = bounds[g], bounds[g + 1]
+        Zg = Z[r0:r1]
+        st, th, _, _, piv = _solve_sums(S - (Zg * w[r0:r1, None]).T @ Zg, want_v=False)
+        if st != 0:
+            return plain + (2, None, None, (np.nan, piv), None, None)
+        jpiv = min(jpiv, piv)
+        refit[g] = th
+        pres[r0:r1] = sw[r0:r1] * (y[r0:r1] - X[r0:r1] @ th)
+        gpress[g] = _chunk_sum(pres[r0:r1] * pres[r0:r1])
+    fm = ft(m)
+    mgf = mg.astype(X.dtype)
+    diff = theta[None, :] - refit
+    thj = theta + _group_sum((1 - mgf / fm)[:, None] * diff)
+    h1 = fm / mgf - 1
+    dev = h1[:, None] * diff - (thj - theta)[None, :]
+    var = _group_sum(dev * dev / h1[:, None]) / ft(ng)
+    jk = np.stack([thj, np.sqrt(var), refit.min(axis=0), refit.max(axis=0)], axis=1)
+    arg = np.argmax(np.abs(refit - theta[None, :]), axis=0).astype(np.int32)  # the first group on ties
+    return plain + (0, jk, arg, (_group_sum(gpress), jpiv), pres, refit)
+
+
 LD_PANEL = 64  # kLdPanel of csrc/host/mvivw_ld_plan.h
 
 
@@ -392,16 +544,56 @@ class HostEngine:
         return theta, se, stats, status, (rho if want_rho else None), ms
 
 
+    def mvivw_jackknife(self, beta, weight, outcome, iv_off, iv, ex_off, ex, grp_off, grp, model=0, want_pres=True,
+                        want_refit=True, dtype=np.float64):
+        """`Engine.mvivw_jackknife`; `dtype` np.longdouble gives the extended-precision form of the tests"""
+        beta, weight = np.asarray(beta, dtype), np.asarray(weight, dtype)
+        iv_off = np.asarray(iv_off, np.int64).reshape(-1)
+        ex_off = np.asarray(ex_off, np.int64).reshape(-1)
+        check_arguments(beta.shape[0], beta.shape[1], np.asarray(outcome, np.int64).reshape(-1), iv_off,
+                        np.asarray(iv, np.int64).reshape(-1), ex_off, np.asarray(ex, np.int64).reshape(-1), model)
+        if grp_off is None:
+            raise ValueError("mvivw: no group offsets")
+        grp_off, grp = np.asarray(grp_off, np.int64).reshape(-1), np.asarray(grp, np.int64).reshape(-1)
+        check_groups(iv_off, ex_off, grp_off, grp)
+        nout = len(iv_off) - 1
+        nex, niv = (int(ex_off.max()), int(iv_off.max())) if nout else (0, 0)
+        ngs = np.maximum(np.diff(grp_off) - 1, 0)
+        refit_off = np.concatenate([[0], np.cumsum(ngs * np.diff(ex_off))]).astype(np.int64)
+        jk, jk_arg = np.full((max(nex, 1), 4), np.nan, dtype), np.full(max(nex, 1), -1, np.int32)
+        jk_stats, jk_status = np.full((nout, 2), np.nan, dtype), np.zeros(nout, np.int32)
+        pres, refit = np.full(max(niv, 1), np.nan, dtype), np.full(max(int(refit_off[-1]), 1), np.nan, dtype)
+
+        def solve(I, E, o, a):
+            r = solve_one_jackknife(beta[np.ix_(I, E)], beta[I, o], weight[I, o], grp[grp_off[a]:grp_off[a + 1]], model)
+            jk_status[a], jk_stats[a] = r[4], r[7]
+            if r[4] == 0:
+                jk[ex_off[a]:ex_off[a + 1]], jk_arg[ex_off[a]:ex_off[a + 1]] = r[5], r[6]
+                pres[iv_off[a]:iv_off[a + 1]] = r[8]
+                refit[refit_off[a]:refit_off[a + 1]] = r[9].reshape(-1)
+            return r[:4]
+
+        theta, se, stats, status, ms = self._run(beta, weight, outcome, iv_off, iv, ex_off, ex, model, solve, dtype=dtype)
+        return (theta, se, stats, status, jk[:nex], jk_arg[:nex], jk_stats, jk_status, pres if want_pres else None,
+                refit if want_refit else None, ms)
+
+
 def run(stem: str, num_samples: int, mode: str = "all", prior_path: str | None = None, ivs_path: str | None = None,
         het: bool = False, model: int = 0, engine=None, data=None, ld: bool = False, ld_ridge: float = 0.0,
-        robust: str | None = None):
+        robust: str | None = None, jackknife=None):
     """The estimates of every outcome of a merged skeleton.  `engine`: a device Engine (skeleton.Engine), or None for the
     numpy form.  `data`: what `ivcheck.load(stem, het)` returned.  Returns a dict: p, selection [(I, E)], theta, se (lists
     per outcome, None unless status 0), stats, status, sk_adj (p x p bool), kernel_ms, ld.  `ld`: the instruments are taken as
     correlated with the marker block corr[p:, p:] of the skeleton as their LD (`mvivw_ld`, ridge `ld_ridge`); stats[:, 2] is
     then the pivot of the LD matrix and status may be 4.  `robust`: None, "huber" or "bisquare" (`mvivw_robust`): stats is
     then nout x 6 (rss, scale, tau, pivot, updates, sum of rho), status may be 5 or 6, and the dict has robust (the name) and
-    rho (per outcome the final rho of its instruments in the order of I, None unless status 0)."""
+    rho (per outcome the final rho of its instruments in the order of I, None unless status 0).  `jackknife`: None, "loo",
+    a number of groups B >= 2, or a non-decreasing integer label per marker row (`groups`; `mvivw_jackknife`): the dict then
+    has jackknife (True), bounds (per outcome the group boundaries), jk_status, jk_stats (nout x 2: PRESS, pivot) and, per
+    outcome and None unless jk_status 0, jk (k x 4: theta_J, se_J, min, max), jk_arg, pres and refit (ng x k)."""
+    if jackknife is not None and (ld or robust is not None):
+        raise ValueError("mvivw: jackknife with ld or robust: whitening mixes the rows, and a reweighted refit per deletion "
+                         "is another estimator")
     if robust is not None and robust not in PSI:
         raise ValueError(f"mvivw: robust {robust!r} is not huber or bisquare")
     if robust is not None and ld:
@@ -419,7 +611,31 @@ def run(stem: str, num_samples: int, mode: str = "all", prior_path: str | None =
     eng = engine if engine is not None else HostEngine()
     if ld_ridge != 0.0 and not ld:
         raise ValueError("mvivw: ld_ridge without ld")
-    if ld:
+    extra = {}
+    if jackknife is not None:
+        if isinstance(jackknife, str) or np.ndim(jackknife) == 0:
+            if jackknife != "loo" and not (isinstance(jackknife, (int, np.integer)) and not isinstance(jackknife, bool)):
+                raise ValueError(f"mvivw: jackknife {jackknife!r} is not loo, a number of groups or a list of labels")
+            bounds = [groups(I, jackknife) for I, _ in selection]
+        else:
+            labels = np.asarray(jackknife)
+            if labels.shape != (beta.shape[0],):
+                raise ValueError(f"mvivw: {labels.size} group labels for {beta.shape[0]} marker rows")
+            bounds = [groups(I, "labels", labels) for I, _ in selection]
+        grp_off = np.zeros(p + 1, np.int64)
+        grp_off[1:] = np.cumsum([len(b) for b in bounds])
+        theta, se, stats, status, jk, jk_arg, jk_stats, jk_status, pres, refit, ms = eng.mvivw_jackknife(
+            beta, weight, np.arange(p, dtype=np.int32), iv_off, iv, ex_off, ex, grp_off, np.concatenate(bounds).astype(np.int32), model)
+        rf_off = np.concatenate([[0], np.cumsum([(len(b) - 1) * len(E) for b, (_, E) in zip(bounds, selection)])])
+        jok = [int(jk_status[o]) == 0 for o in range(p)]
+        extra = {"jackknife": True, "bounds": bounds, "jk_status": np.asarray(jk_status[:p]).copy(),
+                 "jk_stats": np.asarray(jk_stats[:p]).copy(),
+                 "jk": [np.array(jk[ex_off[o]:ex_off[o + 1]]) if jok[o] else None for o in range(p)],
+                 "jk_arg": [np.array(jk_arg[ex_off[o]:ex_off[o + 1]]) if jok[o] else None for o in range(p)],
+                 "pres": [np.array(pres[iv_off[o]:iv_off[o + 1]]) if jok[o] else None for o in range(p)],
+                 "refit": [np.array(refit[rf_off[o]:rf_off[o + 1]]).reshape(len(bounds[o]) - 1, -1) if jok[o] else None
+                           for o in range(p)]}
+    elif ld:
         theta, se, stats, status, ms = eng.mvivw_ld(beta, weight, np.ascontiguousarray(corr[p:, p:], dtype=np.float64),
                                                     np.arange(p, dtype=np.int32), iv_off, iv, ex_off, ex, model, ridge=ld_ridge)
     elif robust is not None:
@@ -428,8 +644,8 @@ def run(stem: str, num_samples: int, mode: str = "all", prior_path: str | None =
     else:
         theta, se, stats, status, ms = eng.mvivw(beta, weight, np.arange(p, dtype=np.int32), iv_off, iv, ex_off, ex, model)
     ok = [int(status[o]) == 0 for o in range(p)]
-    extra = {} if robust is None else {
-        "robust": robust, "rho": [np.array(rho[iv_off[o]:iv_off[o + 1]]) if ok[o] else None for o in range(p)]}
+    if robust is not None:
+        extra = {"robust": robust, "rho": [np.array(rho[iv_off[o]:iv_off[o + 1]]) if ok[o] else None for o in range(p)]}
     return {**extra, "p": p, "selection": selection, "status": np.asarray(status[:p]).copy(), "stats": np.asarray(stats[:p]).copy(),
             "theta": [np.array(theta[ex_off[o]:ex_off[o + 1]]) if ok[o] else None for o in range(p)],
             "se": [np.array(se[ex_off[o]:ex_off[o + 1]]) if ok[o] else None for o in range(p)],
@@ -445,8 +661,10 @@ def write_results(path: str, res) -> None:
     from scipy.special import ndtr
 
     p = res["p"]
+    with_jk = bool(res.get("jackknife"))
     with open(path, "w") as f:
-        f.write("source\tsink\teffect\tp\tsk_adj\tnum_snps\tse\n")
+        f.write("source\tsink\teffect\tp\tsk_adj\tnum_snps\tse" + ("\tjk_effect\tjk_se\tjk_p\tjk_min\tjk_max\tjk_marker" if with_jk else "")
+                + "\n")
         for o in range(p):
             I, E = res["selection"][o]
             st = int(res["status"][o])
@@ -456,9 +674,21 @@ def write_results(path: str, res) -> None:
             elif st == 4:
                 print(f"mvivw: outcome trait {o + 1} (1-based): status 4, the LD matrix of its instruments is not positive "
                       "definite to eight digits, no estimates; try --ld-ridge, or prune-bed at a smaller r", file=sys.stderr)
+            jst = int(res["jk_status"][o]) if with_jk else 0
+            if with_jk and st == 0 and jst in (1, 2):
+                print(f"mvivw: outcome trait {o + 1} (1-based): jackknife status {jst}, no jackknife estimates", file=sys.stderr)
             for e in range(p):
                 if e == o:
                     continue
+                tail = ""
+                if with_jk and e in pos and jst == 0:
+                    tj, sj, lo, hi = (float(v) for v in res["jk"][o][pos[e]])
+                    first = int(I[int(res["bounds"][o][int(res["jk_arg"][o][pos[e]])])]) + 1
+                    with np.errstate(all="ignore"):
+                        pj = 2.0 * ndtr(-abs(np.float64(tj) / np.float64(sj)))
+                    tail = "\t" + "\t".join((_g(tj), _g(sj), _g(pj), _g(lo), _g(hi), str(first)))
+                elif with_jk:
+                    tail = "\tNA" * 6
                 if e not in pos or st == 1:
                     eff, pv, se = "0", "1", "NA"  # the reference's fill
                 elif st != 0:
@@ -468,7 +698,7 @@ def write_results(path: str, res) -> None:
                     with np.errstate(all="ignore"):
                         eff, pv, se = _g(th), _g(2.0 * ndtr(-abs(np.float64(th) / np.float64(s)))), _g(s)
                 adjacent = "TRUE" if res["sk_adj"][e, o] else "FALSE"
-                f.write(f"{e + 1}\t{o + 1}\t{eff}\t{pv}\t{adjacent}\t{len(I)}\t{se}\n")
+                f.write(f"{e + 1}\t{o + 1}\t{eff}\t{pv}\t{adjacent}\t{len(I)}\t{se}{tail}\n")
 
 
 def write_outcomes(path: str, res) -> None:
@@ -478,10 +708,11 @@ def write_outcomes(path: str, res) -> None:
     and sigma = sqrt(q / (m - k))"""
     from scipy.stats import chi2
 
-    with_ld, robust = bool(res.get("ld")), res.get("robust") is not None
+    with_ld, robust, with_jk = bool(res.get("ld")), res.get("robust") is not None, bool(res.get("jackknife"))
     with open(path, "w") as f:
         f.write("sink\tn_exposures\tnum_snps\tsigma\tq\tq_p\tstatus" + ("\tld_pivot" if with_ld else "")
-                + ("\tscale\ttau\titerations\trho_sum" if robust else "") + "\n")
+                + ("\tscale\ttau\titerations\trho_sum" if robust else "")
+                + ("\tjk_groups\tpress\tjk_pivot\tjk_status" if with_jk else "") + "\n")
         for o in range(res["p"]):
             I, E = res["selection"][o]
             st = int(res["status"][o])
@@ -500,6 +731,10 @@ def write_outcomes(path: str, res) -> None:
                 r = res["stats"][o]
                 tail += "\t" + ("\t".join((_g(float(r[1])), _g(float(r[2])), str(int(r[4])), _g(float(r[5])))) if st == 0
                                 else "NA\tNA\tNA\tNA")
+            if with_jk:
+                jst, (press, jpiv) = int(res["jk_status"][o]), (float(v) for v in res["jk_stats"][o])
+                tail += (f"\t{len(res['bounds'][o]) - 1}\t" + (_g(press) if jst == 0 else "NA") + "\t"
+                         + (_g(jpiv) if np.isfinite(jpiv) else "NA") + f"\t{jst}")
             f.write(f"{o + 1}\t{len(E)}\t{len(I)}\t" + "\t".join(cols) + f"\t{st}{tail}\n")
 
 
@@ -515,3 +750,32 @@ def write_weights(path: str, res) -> None:
             I = res["selection"][o][0]
             for j in np.flatnonzero(np.asarray(rho) < 1.0):
                 f.write(f"{o + 1}\t{int(I[j]) + 1}\t{_g(float(rho[j]))}\n")
+
+
+def write_jackknife_residuals(path: str, res) -> None:
+    """`--jackknife-residuals`: `sink marker group press_residual` for every instrument of an outcome of jk_status 0; sink,
+    marker (counted from the first marker) and group 1-based"""
+    with open(path, "w") as f:
+        f.write("sink\tmarker\tgroup\tpress_residual\n")
+        for o in range(res["p"]):
+            if res["pres"][o] is None:
+                continue
+            I, b = res["selection"][o][0], res["bounds"][o]
+            grp = np.repeat(np.arange(len(b) - 1), np.diff(b))
+            for j in range(len(I)):
+                f.write(f"{o + 1}\t{int(I[j]) + 1}\t{int(grp[j]) + 1}\t{_g(float(res['pres'][o][j]))}\n")
+
+
+def write_jackknife_table(path: str, res) -> None:
+    """`--jackknife-table`: `sink group first_marker last_marker n source effect`, the estimate of every exposure without
+    each group, for the outcomes of jk_status 0; all numbers 1-based, markers counted from the first marker"""
+    with open(path, "w") as f:
+        f.write("sink\tgroup\tfirst_marker\tlast_marker\tn\tsource\teffect\n")
+        for o in range(res["p"]):
+            if res["refit"][o] is None:
+                continue
+            (I, E), b = res["selection"][o], res["bounds"][o]
+            for g in range(len(b) - 1):
+                head = f"{o + 1}\t{g + 1}\t{int(I[b[g]]) + 1}\t{int(I[b[g + 1] - 1]) + 1}\t{int(b[g + 1] - b[g])}"
+                for j, t in enumerate(E):
+                    f.write(f"{head}\t{int(t) + 1}\t{_g(float(res['refit'][o][g][j]))}\n")

@@ -986,6 +986,48 @@ class Engine:
                                             _ptr(status), _ptr(rho) if want_rho else None, _ptr(ms)))
         return theta, se, stats[:nout], status[:nout], rho, float(ms[0])
 
+    def mvivw_jackknife(self, beta, weight, outcome, iv_off, iv, ex_off, ex, grp_off, grp, model=0, want_pres=True,
+                        want_refit=True, guard=0):
+        """`mvivw` with delete-group refits (cusk_mvivw_jackknife; the rule is stated in include/cusk_hip.h):
+        `grp[grp_off[a]:grp_off[a + 1]]` are the group boundaries of outcome a, list positions strictly ascending from 0 to
+        its number of instruments (`mvivw.groups` builds them).  Returns (theta, se, stats, status, jk, jk_arg, jk_stats,
+        jk_status, pres, refit, kernel_ms): the first four as `mvivw`; jk nex x 4 (theta_J, se_J, min, max) and jk_arg at the
+        positions of `ex`; jk_stats nout x 2 (PRESS, pivot); pres in the layout of `iv` and refit (theta_-g, outcome-major,
+        then group, then exposure), each None unless wanted.  `guard`: that many extra entries behind every output array
+        are filled with a mark and checked after the call (the tests' guard words)."""
+        beta, weight, outcome, iv_off, iv, ex_off, ex, _, _, _, _ = self._mvivw_args(
+            beta, weight, outcome, iv_off, iv, ex_off, ex, None, None, None, None)
+        (M, p), nout = beta.shape, outcome.shape[0]
+        grp_off = None if grp_off is None else np.ascontiguousarray(grp_off, np.int64).reshape(-1)
+        grp = np.zeros(1, np.int32) if grp is None else np.ascontiguousarray(grp, np.int32).reshape(-1)
+        if grp_off is not None:
+            assert grp_off.shape[0] == nout + 1 and grp.shape[0] >= (int(grp_off.max()) if nout else 0)
+            nrefit = int(np.sum(np.maximum(np.diff(grp_off) - 1, 0) * np.diff(ex_off))) if nout else 0
+        else:
+            nrefit = 0
+        nex, niv = (int(ex_off.max()), int(iv_off.max())) if nout else (0, 0)
+        MARK, IMARK = -777.0, -777
+        sizes = dict(theta=nex, se=nex, stats=3 * nout, jk=4 * nex, jk_stats=2 * nout, pres=niv, refit=nrefit)
+        out = {name: np.full(max(n, 1) + guard, MARK if guard else np.nan) for name, n in sizes.items()}
+        ints = {name: np.full(max(n, 1) + guard, IMARK if guard else 0, np.int32)
+                for name, n in dict(status=nout, jk_arg=nex, jk_status=nout).items()}
+        ms = np.zeros(1, np.float32)
+        self._check(lib().cusk_mvivw_jackknife(
+            self.h, _ptr(beta), _ptr(weight), M, p, nout, _ptr(outcome), _ptr(iv_off), _ptr(iv), _ptr(ex_off), _ptr(ex),
+            None if grp_off is None else _ptr(grp_off), _ptr(grp), int(model), _ptr(out["theta"]), _ptr(out["se"]),
+            _ptr(out["stats"]), _ptr(ints["status"]), _ptr(out["jk"]), _ptr(ints["jk_arg"]), _ptr(out["jk_stats"]),
+            _ptr(ints["jk_status"]), _ptr(out["pres"]) if want_pres else None, _ptr(out["refit"]) if want_refit else None,
+            _ptr(ms)))
+        if guard:
+            sizes.update(status=nout, jk_arg=nex, jk_status=nout)
+            for name, arr in {**out, **ints}.items():
+                if not np.all(arr[max(sizes[name], 1):] == (IMARK if arr.dtype == np.int32 else MARK)):
+                    raise RuntimeError(f"cusk_mvivw_jackknife wrote behind {name}")
+        return (out["theta"][:max(nex, 1)], out["se"][:max(nex, 1)], out["stats"][:3 * nout].reshape(nout, 3), ints["status"][:nout],
+                out["jk"][:4 * nex].reshape(nex, 4), ints["jk_arg"][:nex], out["jk_stats"][:2 * nout].reshape(nout, 2),
+                ints["jk_status"][:nout], out["pres"][:max(niv, 1)] if want_pres else None,
+                out["refit"][:max(nrefit, 1)] if want_refit else None, float(ms[0]))
+
     def abs_median(self, vals, seg_off, out=None):
         """The exact median of |vals[seg_off[g]:seg_off[g + 1]]| per segment (cusk_abs_median), NaN for an empty one.
         `out` may be given (float64, at least one entry per segment) to be filled in place."""

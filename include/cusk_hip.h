@@ -134,7 +134,9 @@ const char *cusk_last_error(const cusk_engine *e);
  * cusk_sepselect_greedy for candidate lists too long for LDS, default 4 GiB; such pairs run in batches of what fits), "mvivw_part_bytes" (HBM of cusk_mvivw's chunk partials alive at
  * once, default 256 MiB; outcomes run in groups of what fits, an outcome that alone exceeds it as a group of its own; the
  * results do not depend on it), "mvivw_ld_bytes" (HBM of cusk_mvivw_ld's m x m workspace, default 8 GiB; an outcome that
- * needs more is an argument error), "phen_rint_bytes" (HBM of cusk_phen_rint's sorted keys and ranks alive at once, default
+ * needs more is an argument error), "mvivw_jk_bytes" (HBM of cusk_mvivw_jackknife's refitted estimates alive at once, default
+ * 1 GiB; outcomes run in batches of what fits, an outcome that alone exceeds it as a batch of its own; the results do not
+ * depend on it), "phen_rint_bytes" (HBM of cusk_phen_rint's sorted keys and ranks alive at once, default
  * 1 GiB; traits run in groups of what fits, the results do not depend on it, and a single trait that needs more is an
  * argument error). */
 int cusk_engine_set_option(cusk_engine *e, const char *key, long long value);
@@ -840,6 +842,65 @@ int cusk_mvivw_robust(cusk_engine *e, const double *beta, const double *weight, 
  * values are ordered by the bit patterns of their absolute values: -0.0 counts as 0, a NaN lies above every number.
  * Argument errors: a null pointer, offsets that are negative or not monotone, a segment of 2^31 values or more. */
 int cusk_abs_median(cusk_engine *e, const double *vals, const long long *seg_off, int nseg, double *out);
+
+/* `mvivw --jackknife`: the regressions of cusk_mvivw refitted without each group of an outcome's instruments.  With groups
+ * of one instrument that is the leave-one-out table and its prediction residual sum of squares (PRESS); with contiguous
+ * blocks of markers it is the delete-one-block jackknife, whose standard error needs no LD matrix.
+ * Nothing in the reference computes this and nothing here was compared with R, MR-PRESSO or LDSC.  PRESS is what MR-PRESSO
+ * calls the observed global residual sum of squares; the p-value of its global test needs a simulated null and is not
+ * computed.  The block jackknife assumes groups wider than the LD range.
+ * All pointers are HOST memory.  beta, weight, M, p, outcome, iv_off/iv, ex_off/ex, model, X = beta[I, E], y = beta[I, o],
+ * w = weight[I, o], m = |I|, k = |E| are those of cusk_mvivw.
+ *   grp_off/grp  nout + 1 offsets into grp; grp = for outcome a its ng + 1 group boundaries, list positions of the outcome's
+ *                instrument list, strictly ascending, the first 0 and the last m.  Group g is the run of list positions
+ *                [grp[g], grp[g + 1]) and has m_g rows.  An outcome with m = 0 has no boundary, or the single boundary 0.
+ * The rule per outcome, IEEE double throughout, no floating-point atomics, every sum in the one order stated: two runs
+ * give the same bytes, and an outcome's result depends neither on the other outcomes of the call nor on the engine
+ * options "mvivw_part_bytes" and "mvivw_jk_bytes".
+ *   0. The plain fit: steps 1 - 5 of cusk_mvivw give theta, se, stats and status, bit for bit what cusk_mvivw returns for
+ *      the same call; G and b are the chunk-ordered sums of its step 1.  status != 0: jk_status is that status and nothing
+ *      more is computed.
+ *   1. Precondition: ng < 2, or a group with m - m_g <= k: jk_status 1, nothing more is computed.
+ *   2. Per group g: G_g = sum_{i in g} (w_i x_i) x_i' and b_g = sum_{i in g} (w_i x_i) y_i, each entry one chain of fused
+ *      multiply-adds from +0 over the group's rows in ascending order, w_i x_ij rounded first.  A = G - G_g, c = b - b_g,
+ *      entry by entry.
+ *   3. d_j = sqrt(A_jj), As = A / (d d') with a unit diagonal, Cholesky of As with the pivot rule and both substitutions
+ *      exactly as steps 2 - 3 of cusk_mvivw (v is not formed): theta_-g = D^-1 As^-1 D^-1 c.  A squared pivot below
+ *      CUSK_PHEN_PIVOT_MIN or an A_jj that is not positive in any group: jk_status 2; the pivot reported is that of the
+ *      first such group in group order (0 for an A_jj that is not positive), and every other jackknife output of the
+ *      outcome is NaN.
+ *   4. Prediction residuals: for i in g, r_i = sqrt(w_i) (y_i - x_i theta_-g), x_i theta_-g one chain of fused multiply-adds
+ *      from +0 over the exposures in list order.  The r_i^2 of a group are summed in runs of 256 consecutive rows from the
+ *      group's first row, each run in the order of cusk_mvivw's chunk sums, the runs added in run order; PRESS is the sum
+ *      of the group sums in the order of step 5.
+ *   5. The weighted delete-group jackknife (Busing, Meijer, van der Leeden 1999) for unequal groups, per exposure j.  With
+ *      h_g = m / m_g, every sum over groups taken in chunks of 256 consecutive groups, inside a chunk in ascending order
+ *      from +0, the chunk sums added in chunk order:
+ *        theta_J = theta + sum_g (1 - m_g / m) (theta - theta_-g)          (= ng theta - sum_g (1 - m_g / m) theta_-g)
+ *        var_J   = (1 / ng) sum_g ((h_g - 1) (theta - theta_-g) - (theta_J - theta))^2 / (h_g - 1)
+ *                                       (= (1 / ng) sum_g (tau_g - theta_J)^2 / (h_g - 1), tau_g = h_g theta - (h_g - 1) theta_-g)
+ *        se_J    = sqrt(var_J)
+ *      evaluated in the first forms, which do not cancel; h_g - 1 is m / m_g - 1.  With equal groups se_J is the textbook
+ *      sqrt((ng - 1) / ng sum (theta_-g - mean)^2).  Also min_g and max_g of theta_-g,j, and the group with the largest
+ *      |theta_-g,j - theta_j|, the first such group on ties.  model does not enter steps 1 - 5.
+ * Out: theta, se, stats, status as cusk_mvivw (step 0).  jk nex x 4 at the positions of ex: theta_J, se_J, min, max.  jk_arg
+ * at the positions of ex: the most influential group, -1 where jk_status != 0.  jk_stats nout x 2: PRESS; the smallest
+ * squared pivot over all groups (jk_status 0) or the one that failed (jk_status 2), else NaN.  jk_status nout ints: 0; 1
+ * (step 1, or the plain status 1); 2 (step 3, or the plain status 2); 3 (the plain status).  pres (may be NULL; layout of
+ * iv, only [iv_off[0], iv_off[nout]) is written): r_i.  refit (may be NULL): sum_a ng_a k_a doubles, outcome-major, then
+ * group, then exposure: theta_-g; an outcome with m = 0 and no boundary has ng = 0.  For jk_status != 0 the outcome's jk,
+ * PRESS, pres and refit are NaN.
+ * Argument errors (CUSK_ERR_ARG, nothing launched, nothing written): those of cusk_mvivw; grp_off null; boundaries that are
+ * not strictly ascending from 0 to m; an outcome with m > 0 and no groups (fewer than two boundaries).
+ * One workgroup refits one (outcome, group): the cost is ng (k^3 / 3 + m_g k^2 / 2) multiply-adds per outcome.  The
+ * refitted estimates (ng k doubles per outcome) stay on the device in batches of at most 1 GiB (engine option
+ * "mvivw_jk_bytes").  kernel_ms (may be NULL): device time from the first to the last kernel, with refit the copies of
+ * the batches included. */
+int cusk_mvivw_jackknife(cusk_engine *e, const double *beta, const double *weight, long long M, int p, int nout,
+                         const int *outcome, const long long *iv_off, const int *iv, const int *ex_off, const int *ex,
+                         const long long *grp_off, const int *grp, int model, double *theta, double *se, double *stats,
+                         int *status, double *jk, int *jk_arg, double *jk_stats, int *jk_status, double *pres, double *refit,
+                         float *kernel_ms);
 
 /* out_host[a*k + b] = M_dev[idx[a]*n + idx[b]]: the retained sub-matrix of parent_set.cpp:84-238
  * (reduce_gc / reduce_gcs) without copying the n*n matrix to the host; idx_host has k entries. */
